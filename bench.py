@@ -23,16 +23,23 @@ all-reduce of the tally buffer per step), so the per-N lines compare.
 on 8 GPUs, BASELINE configs[3]).
 
     python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c4]
+    python bench.py --full ...                          (+ cpu_baseline, fp_offclamp)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
+A plain run sets up, spins the census up, warms up, times the K steps, writes
+the last timed step's outputs (`--dump-outputs DIR`) and prints the line; the
+legs that take runs of their own (`cpu_baseline`, `kernels.fp_offclamp`) run
+only with `--full`.
+
 Rank 0 prints ONE JSON line.  `value` = packet-steps of all ranks / the max
-over ranks of the wall time of the K timed steps.  `roofline` prices the
+over ranks of the wall time of the K timed steps; `ms_per_step` = that wall
+time / K in milliseconds.  `roofline` prices the
 dominant kernel (generation-0 transport launch) at 160 algorithmic bytes
 (an 80-B packet record in + out) per lane path-step, the
 pass through the geometry block that a probe bundle shares among its copies,
 and carries its measured HBM bytes and VALU-issue fraction from the committed
 PMC profile of the same command; `kernels` reports the FP and table kernels beside it;
-`cpu_baseline` times the reference's algorithm (the C oracle in its
+`cpu_baseline` (with `--full`) times the reference's algorithm (the C oracle in its
 reference mode: per-copy probes, lagged-Fibonacci streams with the
 per-census-packet reseed, bit-exact to the Fortran) on the host's CPU share,
 on a strided sample of the GPU's own final census plus the same fraction of
@@ -305,6 +312,27 @@ def load_pmc(workload_key: str):
         return {}
 
 
+DUMP_OUTPUTS_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays: dict) -> None:
+    """--dump-outputs: every array as <name>.npy in float64.  Should the arrays
+    exceed DUMP_OUTPUTS_MAX_BYTES in all, each array over its equal share is
+    cut to a fixed sample of its flattened elements (sorted indices drawn with
+    seed 0, so two runs with the same arguments keep the same elements)."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_OUTPUTS_MAX_BYTES:
+        share = DUMP_OUTPUTS_MAX_BYTES // (8 * len(arrays))
+        for k, a in arrays.items():
+            if a.size > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+                arrays[k] = a.reshape(-1)[idx]
+    for k, a in arrays.items():
+        np.save(d / (k + ".npy"), a)
+
+
 def census_capacity(sources: int, per_source: float, free: float, side: float, inplace: int) -> int:
     """Census records the run may hold: per_source x sources, within 85 % of
     the free HBM beside the event and packet buffers."""
@@ -500,14 +528,24 @@ def main():
                          "bit-identical to the oracle)")
     ap.add_argument("--host-tables", action="store_true",
                     help="c3: move tables/electrons through host arrays every step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: "
+                         "c3 on one GPU: cpu_baseline and kernels.fp_offclamp (off by default: a "
+                         "plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip cpu_baseline and fp_offclamp's CPU leg")
     ap.add_argument("--no-fp-offclamp", action="store_true",
-                    help="c3: skip the untimed off-clamp FP update (kernels.fp_offclamp)")
+                    help="with --full, c3: skip the untimed off-clamp FP update (kernels.fp_offclamp)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dump", default=None,
                     help="directory: each rank writes rank<r>.npz with the last timed step's tally "
                          "buffer, and for c3 the timed steps' SED sums and the electron state "
                          "(the N-rank rehearsal compares them, tests/test_gpu_bench_ranks.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="directory: rank 0 writes what the last timed step returned as DIR/<name>.npy "
+                         "(float64): the tally buffer, the timed steps' SED (c5: light-curve) sums "
+                         "and for c3 the electron state (at most %d MB in all)"
+                         % (DUMP_OUTPUTS_MAX_BYTES >> 20))
     args = ap.parse_args()
 
     import torch
@@ -579,6 +617,19 @@ def main():
             blob.update(sed_F=F, sed_F2=F2, sed_count=cnt, f_nt=f_nt, Pnt=Pnt,
                         tea=np.asarray(run.state["tea"]), Te_new=np.asarray(run.state["Te_new"]))
         np.savez(d / ("rank%d.npz" % rank), **blob)
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: the
+        # step's (all-reduced) tally buffer, the SED / light-curve sums the
+        # timed steps binned, and for c3 the electron state the FP update left
+        outs = {"tallies": last_tallies}
+        if wk in ("c3", "c5"):
+            F, F2, cnt, _ = eng.obs_result()
+            outs.update(obs_F=F, obs_F2=F2, obs_count=cnt)
+        if wk == "c3":
+            f_nt, Pnt = run.electrons()
+            outs.update(f_nt=f_nt, Pnt=Pnt, tea=np.asarray(run.state["tea"]),
+                        Te_new=np.asarray(run.state["Te_new"]))
+        dump_outputs(args.dump_outputs, outs)
     if rank != 0:
         eng.close()
         return
@@ -733,9 +784,9 @@ def main():
         "kernels": kernels,
         "cpu_baseline": None,
     }
-    if world == 1 and not args.no_cpu_baseline and wk == "c3":
+    if args.full and world == 1 and not args.no_cpu_baseline and wk == "c3":
         out["cpu_baseline"] = cpu_baseline(eng, run, args.cpu_seconds)
-    if world == 1 and wk == "c3" and not args.no_fp_offclamp:
+    if args.full and world == 1 and wk == "c3" and not args.no_fp_offclamp:
         kernels["fp_offclamp"] = fp_offclamp(local, cpu=not args.no_cpu_baseline)
     print(json.dumps(out))
     eng.close()

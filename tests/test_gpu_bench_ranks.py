@@ -43,9 +43,10 @@ def test_two_ranks_on_one_gpu_match_one_rank(workload, spinup, tmp_path):
               "--no-cpu-baseline", "--no-fp-offclamp"]
     d1, d2 = tmp_path / "one", tmp_path / "two"
     one = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--sources", "8000000",
-                          "--dump", str(d1)] + common,
+                          "--dump", str(d1), "--dump-outputs", str(d1 / "outputs")] + common,
                          capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
+    _check_dumped_outputs(workload, _last_json(one.stdout), d1)
     env = dict(os.environ, C2D_ONE_GPU="1", C2D_DIST_BACKEND="gloo")
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                           "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -61,6 +62,25 @@ def test_two_ranks_on_one_gpu_match_one_rank(workload, spinup, tmp_path):
         assert b["config"]["census"]["layout"].startswith("chunked")
         assert a["config"]["census"]["records_after_spinup"] > 0
     _compare_results(workload, d1, d2)
+
+
+def _check_dumped_outputs(workload, line, d1):
+    """bench.py --dump-outputs: the last timed step's results as float64 .npy
+    files, the same arrays --dump holds; a run without --full has no legs
+    beyond its timed steps, and --steps is the number of steps timed."""
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["cpu_baseline"] is None and "fp_offclamp" not in line["kernels"]
+    ref = np.load(d1 / "rank0.npz")
+    names = {"tallies": "tallies"}
+    if workload == "c3":
+        names.update(obs_F="sed_F", obs_F2="sed_F2", obs_count="sed_count", f_nt="f_nt", Pnt="Pnt",
+                     tea="tea", Te_new="Te_new")
+    files = sorted(p.name for p in (d1 / "outputs").glob("*"))
+    assert files == sorted(k + ".npy" for k in names)
+    for k, r in names.items():
+        x = np.load(d1 / "outputs" / (k + ".npy"))
+        assert x.dtype == np.float64
+        np.testing.assert_array_equal(x, np.asarray(ref[r], np.float64), err_msg=k)
 
 
 def _rel(a, b):

@@ -8,7 +8,7 @@
 #   tests          the whole `pytest -m gpu` suite, one process
 #   tests:<files>  some test files (comma-separated, under tests/)
 #   smoke          __graft_entry__.smoke()
-#   bench          bench.py with the driver's defaults (C3, N=1, with cpu_baseline)
+#   bench          bench.py --full with the driver's defaults (C3, N=1, with cpu_baseline and fp_offclamp)
 #   c3 | c3chunk | c4 | c5   bench.py workloads without cpu_baseline (STEPS/WARMUP)
 #   ab:<t1>,<t2>   bench each tuning build compton2d_amd/sweep/<t>/ (tools/build_sweep.sh;
 #                  "base" = the in-tree library), SPINUP/STEPS/WARMUP
@@ -56,7 +56,7 @@ for r in "$@"; do
     smoke)
       run 300 smoke python -c "import __graft_entry__ as g; g.smoke()"; tail -2 "$O/smoke.out" ;;
     bench)
-      run 600 bench python bench.py; line "$O/bench.out" ;;
+      run 600 bench python bench.py --full; line "$O/bench.out" ;;
     c3)      run 500 c3 python bench.py --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-fp-offclamp; line "$O/c3.out" ;;
     c3chunk) run 500 c3chunk python bench.py --steps $STEPS --warmup $WARMUP --no-cpu-baseline --census-inplace 1
              line "$O/c3chunk.out" ;;
