@@ -503,6 +503,7 @@ class FpCall:
 # ---------------------------------------------------------------------------
 OBS_SED, OBS_LC = 0, 1
 OBS_MAX_T, OBS_MAX_MU, OBS_MAX_E = 1024, 32, 256
+OBS_SET_MAX = 8                 # C2D_OBS_SET_MAX: members of an observer set (c2d_obs_set_*)
 
 
 class ObsBins(C.Structure):

@@ -455,6 +455,29 @@ struct ObsDev {
   int32_t sorted_t, sorted_mu, sorted_e;   /* lo[] and hi[] non-decreasing: binary search */
 };
 
+/* ---- observer sets: several binnings in one pass (observe.hip c2d_obs_set_kernel) ---- */
+constexpr int OBS_SET_MAX = 8;               /* C2D_OBS_SET_MAX */
+constexpr int OBS_SET_LDS = 64 * 1024;       /* a set workgroup's LDS, static part included */
+constexpr int OBS_SET_LDS_STATIC = 1024;     /* reserved for the kernel's static tables */
+
+struct ObsSetMember {
+  double gam_bulk, rmax, t_offset;
+  double* F; double* F2; double* cnt;        /* [n_t][n_mu][n_e] each, as ObsDev */
+  int32_t mode, n_t, n_mu, n_e;
+  int32_t lds_rows;                          /* leading time rows privatised in LDS (0..n_t) */
+  int32_t sorted_t, sorted_mu, sorted_e;
+  /* offsets in doubles into the workgroup's dynamic LDS: the member's edges
+   * (t0 t1 mu0 mu1 E0 E1 back to back; the same offset into ObsSetDev.edges)
+   * and its three privatised histograms (F, F2, count: lds_rows rows each) */
+  int32_t edge_off, hist_off;
+};
+
+struct ObsSetDev {
+  const double* edges;                       /* every member's edges, n_edges doubles */
+  int32_t n, n_edges, n_hist;                /* members; LDS doubles of edges / of histograms */
+  ObsSetMember m[OBS_SET_MAX];
+};
+
 }  // namespace c2d
 
 #endif

@@ -21,6 +21,7 @@
 #include "c2d_math.h"
 #include "c2d_rng.h"
 #include "pspt_host.h"
+#include "plcm_host.h"
 
 using namespace c2d;
 
@@ -55,6 +56,8 @@ extern "C" int c2d_launch_obs_segs(const ObsDev* O, const double* const* ev, con
                                    int grid, hipStream_t stream);
 extern "C" int c2d_launch_obs(const ObsDev* O, const double* ev, int64_t n, int grid,
                               hipStream_t s);
+extern "C" int c2d_launch_obs_set(const ObsSetDev* Q, const double* const* ev, const int64_t* n, int nseg,
+                                  int grid, hipStream_t stream);
 extern "C" size_t c2d_obs_lds_bytes(int n_t, int n_mu, int n_e, int lds_rows);
 extern "C" int c2d_obs_block(void);
 extern "C" int c2d_launch_tridag(const double* a, const double* b, const double* c,
@@ -113,6 +116,16 @@ struct DevCensus {
 };
 
 }  // namespace
+
+/* host side of one member of the observer set (c2d_obs_set_*) */
+struct ObsSetHost {
+  int kind = 0;                               /* 0 raw bins, 1 pspt deck, 2 plcm deck */
+  std::vector<double> edges;                  /* t0 t1 mu0 mu1 E0 E1 */
+  double* hist = nullptr;                     /* F, F2, count: 3 x n_t x n_mu x n_e */
+  double* red = nullptr;                      /* world_sum reduction buffer, same size (decks only) */
+  c2d_pspt_deck pspt;
+  std::vector<c2d_plcm_deck> plcm;            /* one element when kind == 2 */
+};
 
 struct c2d_ctx {
   Geo geo_h;                  /* host copy of the grids (census import's bin lookups) */
@@ -252,6 +265,16 @@ struct c2d_ctx {
   int64_t obs_ev_cap = 0;
   int obs_wg_per_cu = 1;
   double obs_ms = 0.0;
+  /* observer set: several binnings filled in one pass (c2d_obs_set_*); its
+   * asynchronous launch shares obs_stream and the in-flight fence above */
+  ObsSetDev oset = {};
+  std::vector<ObsSetHost> oset_h;
+  double* oset_edges = nullptr;
+  bool oset_started = false;                  /* accumulated since the last clear */
+  bool obs_inflight_set = false;              /* the launch in flight is the set's */
+  int oset_wg_per_cu = 1;
+  int32_t oset_launches = 0;
+  double oset_ms = 0.0;
 };
 
 static int fail(c2d_ctx* c, int code, const char* fmt, ...) {
@@ -515,9 +538,13 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
     if (c->cens[b].tg) (void)hipFree(c->cens[b].tg);
   }
   for (double* p : c->spec_bufs) (void)hipFree(p);
-  void* optrs[] = {c->obs_edges, c->obs_hist, c->obs_ev, c->pspt_red, c->cdf_guide};
+  void* optrs[] = {c->obs_edges, c->obs_hist, c->obs_ev, c->pspt_red, c->cdf_guide, c->oset_edges};
   for (void* p : optrs)
     if (p) (void)hipFree(p);
+  for (ObsSetHost& m : c->oset_h) {
+    if (m.hist) (void)hipFree(m.hist);
+    if (m.red) (void)hipFree(m.red);
+  }
   void* vptrs[] = {c->vem_zin, c->vem_fnt, c->vem_eph, c->vem_kap, c->vem_et, c->vem_eh, c->vem_zout};
   for (void* q : vptrs)
     if (q) (void)hipFree(q);
@@ -2687,7 +2714,8 @@ static int obs_settle(c2d_ctx* c) {
   HIPCHK(c, hipEventSynchronize(c->ev_obs_b));
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ev_obs_a, c->ev_obs_b);
-  c->obs_ms += ms;
+  if (c->obs_inflight_set) c->oset_ms += ms; else c->obs_ms += ms;
+  c->obs_inflight_set = false;
   return C2D_OK;
 }
 
@@ -2841,6 +2869,326 @@ extern "C" int c2d_obs_write_pspt(c2d_ctx* c, const char* path, int32_t factor, 
   const char* out = (path && path[0]) ? path : c->pspt.outfile;
   if (c2d_pspt_write(out, &c->pspt, F.data(), cnt.data(), factor))
     return fail(c, C2D_E_IO, "c2d_obs_write_pspt: cannot write '%s'", out);
+  return C2D_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* observer sets: several SEDs and light curves in one pass            */
+/* ------------------------------------------------------------------ */
+/* The LDS plan of a set: the edges of every member, then
+ * privatised leading time rows.  What the edges leave of the workgroup's
+ * OBS_SET_LDS is shared out equally among the members, each taking whole
+ * rows of its share (at most its n_t); what that leaves over is handed out
+ * in registration order.  -1 when the edges alone do not fit. */
+static int obs_set_plan(ObsSetDev& Q, int* wg_per_cu) {
+  const int64_t budget = (OBS_SET_LDS - OBS_SET_LDS_STATIC) / (int64_t)sizeof(double);
+  int64_t ne = 0;
+  for (int j = 0; j < Q.n; j++) {
+    Q.m[j].edge_off = (int32_t)ne;
+    ne += 2 * ((int64_t)Q.m[j].n_t + Q.m[j].n_mu + Q.m[j].n_e);
+    if (ne > budget) return -1;
+  }
+  int64_t left = budget - ne;
+  const int64_t share = Q.n ? left / Q.n : 0;
+  for (int j = 0; j < Q.n; j++) {
+    const int64_t row = 3 * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
+    Q.m[j].lds_rows = (int32_t)std::min<int64_t>(Q.m[j].n_t, share / row);
+    left -= Q.m[j].lds_rows * row;
+  }
+  int64_t nh = 0;
+  for (int j = 0; j < Q.n; j++) {
+    const int64_t row = 3 * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
+    const int64_t more = std::min<int64_t>(Q.m[j].n_t - Q.m[j].lds_rows, left / row);
+    Q.m[j].lds_rows += (int32_t)more;
+    left -= more * row;
+    Q.m[j].hist_off = (int32_t)(ne + nh);
+    nh += Q.m[j].lds_rows * row;
+  }
+  Q.n_edges = (int32_t)ne;
+  Q.n_hist = (int32_t)nh;
+  /* workgroups per CU that fit the CU's 160 KiB of LDS, at most 4 */
+  const size_t bytes = (size_t)(ne + nh) * sizeof(double) + OBS_SET_LDS_STATIC;
+  *wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / bytes));
+  return 0;
+}
+
+static void obs_set_free(c2d_ctx* c) {
+  for (ObsSetHost& m : c->oset_h) {
+    if (m.hist) (void)hipFree(m.hist);
+    if (m.red) (void)hipFree(m.red);
+  }
+  c->oset_h.clear();
+  if (c->oset_edges) (void)hipFree(c->oset_edges);
+  c->oset_edges = nullptr;
+  c->oset = ObsSetDev{};
+  c->oset_started = false;
+  c->oset_launches = 0;
+  c->oset_ms = 0.0;
+}
+
+extern "C" int c2d_obs_set_clear(c2d_ctx* c) {
+  if (!c) return C2D_E_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }   /* the histograms are about to go */
+  obs_set_free(c);
+  return C2D_OK;
+}
+
+/* add a member: `h` carries its kind and deck; the edges come from `b` */
+static int obs_set_add_member(c2d_ctx* c, const c2d_obs_bins* b, ObsSetHost&& h, int32_t* id, const char* who) {
+  if ((b->mode != C2D_OBS_SED && b->mode != C2D_OBS_LC) || b->n_t < 1 || b->n_t > C2D_OBS_MAX_T ||
+      b->n_mu < 1 || b->n_mu > C2D_OBS_MAX_MU || b->n_e < 1 || b->n_e > C2D_OBS_MAX_E ||
+      !b->t0 || !b->t1 || !b->mu0 || !b->mu1 || !b->E0 || !b->E1 || !(b->gam_bulk >= 1.0))
+    return fail(c, C2D_E_ARG, "%s: bad binning", who);
+  if (b->mode == C2D_OBS_SED && b->n_mu != 1)
+    return fail(c, C2D_E_ARG, "%s: the SED mode has one angular window", who);
+  if (c->oset_started)
+    return fail(c, C2D_E_STATE, "%s: the set has accumulated events; c2d_obs_set_clear first", who);
+  if (c->oset.n >= C2D_OBS_SET_MAX)
+    return fail(c, C2D_E_ARG, "%s: a set holds at most %d members", who, C2D_OBS_SET_MAX);
+  ObsSetDev Q = c->oset;
+  ObsSetMember& M = Q.m[Q.n++];
+  M = ObsSetMember{};
+  M.gam_bulk = b->gam_bulk; M.rmax = b->rmax; M.t_offset = b->t_offset;
+  M.mode = b->mode; M.n_t = b->n_t; M.n_mu = b->n_mu; M.n_e = b->n_e;
+  auto sorted = [](const double* lo, const double* hi, int n) {
+    for (int i = 1; i < n; i++)
+      if (!(lo[i] >= lo[i - 1]) || !(hi[i] >= hi[i - 1])) return 0;
+    return 1;
+  };
+  M.sorted_t = sorted(b->t0, b->t1, b->n_t);
+  M.sorted_mu = sorted(b->mu0, b->mu1, b->n_mu);
+  M.sorted_e = sorted(b->E0, b->E1, b->n_e);
+  int wg = 1;
+  if (obs_set_plan(Q, &wg))
+    return fail(c, C2D_E_ARG, "%s: the set's bin edges (%lld B with this member) exceed the workgroup's %d B of LDS",
+                who, (long long)(sizeof(double) * (2 * ((int64_t)b->n_t + b->n_mu + b->n_e) + c->oset.n_edges)),
+                OBS_SET_LDS - OBS_SET_LDS_STATIC);
+  h.edges.clear();
+  h.edges.insert(h.edges.end(), b->t0, b->t0 + b->n_t);
+  h.edges.insert(h.edges.end(), b->t1, b->t1 + b->n_t);
+  h.edges.insert(h.edges.end(), b->mu0, b->mu0 + b->n_mu);
+  h.edges.insert(h.edges.end(), b->mu1, b->mu1 + b->n_mu);
+  h.edges.insert(h.edges.end(), b->E0, b->E0 + b->n_e);
+  h.edges.insert(h.edges.end(), b->E1, b->E1 + b->n_e);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  /* every member's edges in one device array, in the LDS order of the plan */
+  std::vector<double> all;
+  all.reserve((size_t)Q.n_edges);
+  for (const ObsSetHost& m : c->oset_h) all.insert(all.end(), m.edges.begin(), m.edges.end());
+  all.insert(all.end(), h.edges.begin(), h.edges.end());
+  const size_t nh = (size_t)b->n_t * b->n_mu * b->n_e;
+  double *d_edges = nullptr, *d_hist = nullptr, *d_red = nullptr;
+  hipError_t e = dalloc(&d_edges, all.size());
+  if (e == hipSuccess) e = dalloc(&d_hist, 3 * nh);
+  /* the world_sum reduction buffer lives as long as the member (as pspt_red) */
+  if (e == hipSuccess && h.kind) e = dalloc(&d_red, 3 * nh);
+  if (e == hipSuccess) e = hipMemcpy(d_edges, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_hist, 0, 3 * nh * sizeof(double));
+  if (e != hipSuccess) {
+    if (d_edges) (void)hipFree(d_edges);
+    if (d_hist) (void)hipFree(d_hist);
+    if (d_red) (void)hipFree(d_red);
+    return fail(c, C2D_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  }
+  if (c->oset_edges) (void)hipFree(c->oset_edges);
+  c->oset_edges = d_edges;
+  M.F = d_hist; M.F2 = M.F + nh; M.cnt = M.F2 + nh;
+  Q.edges = d_edges;
+  h.hist = d_hist;
+  h.red = d_red;
+  if (id) *id = Q.n - 1;
+  c->oset = Q;
+  c->oset_wg_per_cu = wg;
+  c->oset_h.push_back(std::move(h));
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_add(c2d_ctx* c, const c2d_obs_bins* b, int32_t* id) {
+  if (!c || !b) return C2D_E_ARG;
+  return obs_set_add_member(c, b, ObsSetHost{}, id, "c2d_obs_set_add");
+}
+
+extern "C" int c2d_obs_set_add_pspt(c2d_ctx* c, const char* deck, int32_t* id) {
+  if (!c) return C2D_E_ARG;
+  ObsSetHost h;
+  h.kind = 1;
+  c2d_pspt_deck& d = h.pspt;
+  if (c2d_pspt_parse(deck ? deck : "", &d))
+    return fail(c, C2D_E_ARG, "c2d_obs_set_add_pspt: the deck's grid has no bins or more than %d energy channels",
+                C2D_PSPT_CHMAX);
+  c2d_obs_bins b;
+  b.mode = C2D_OBS_SED; b.gam_bulk = d.gam_bulk; b.rmax = d.rmax; b.t_offset = 0.0;
+  b.n_t = d.n_t; b.t0 = d.t0; b.t1 = d.t1;
+  b.n_mu = 1; b.mu0 = &d.mu0; b.mu1 = &d.mu1;
+  b.n_e = d.n_e; b.E0 = d.E0; b.E1 = d.E1;
+  return obs_set_add_member(c, &b, std::move(h), id, "c2d_obs_set_add_pspt");
+}
+
+extern "C" int c2d_obs_set_add_plcm(c2d_ctx* c, const char* deck, int32_t* id) {
+  if (!c) return C2D_E_ARG;
+  ObsSetHost h;
+  h.kind = 2;
+  h.plcm.resize(1);
+  c2d_plcm_deck& d = h.plcm[0];
+  if (c2d_plcm_parse(deck ? deck : "", &d))
+    return fail(c, C2D_E_ARG, "c2d_obs_set_add_plcm: the deck has no angular bin, an empty region or more than %d "
+                "energy channels", C2D_PLCM_CHMAX);
+  c2d_obs_bins b;
+  b.mode = C2D_OBS_LC; b.gam_bulk = d.gam_bulk; b.rmax = d.rmax; b.t_offset = d.t_offset;
+  b.n_t = d.n_t; b.t0 = d.t0; b.t1 = d.t1;
+  b.n_mu = d.n_mu; b.mu0 = d.mu0; b.mu1 = d.mu1;
+  b.n_e = d.n_e; b.E0 = d.E0; b.E1 = d.E1;
+  return obs_set_add_member(c, &b, std::move(h), id, "c2d_obs_set_add_plcm");
+}
+
+static int obs_set_grid(const c2d_ctx* c, int64_t tot) {
+  const int64_t bs = c2d_obs_block();
+  return (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * c->oset_wg_per_cu, (tot + bs - 1) / bs));
+}
+
+/* one launch over the segments on the context's stream, waited for */
+static int obs_set_launch_sync(c2d_ctx* c, const double* const* ev, const int64_t* m, int nseg) {
+  int64_t tot = 0;
+  for (int s = 0; s < nseg; s++) tot += m[s];
+  if (tot == 0) return C2D_OK;
+  HIPCHK(c, hipEventRecord(c->ev_g0a, c->stream));
+  const int rc = c2d_launch_obs_set(&c->oset, ev, m, nseg, obs_set_grid(c, tot), c->stream);
+  if (rc) return fail(c, C2D_E_HIP, "obs set launch: %s", hipGetErrorString((hipError_t)rc));
+  HIPCHK(c, hipEventRecord(c->ev_g0b, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ev_g0a, c->ev_g0b);
+  c->oset_ms += ms;
+  c->oset_launches++;
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_accumulate(c2d_ctx* c, const double* events, int64_t n) {
+  if (!c) return C2D_E_ARG;
+  if (c->oset.n < 1) return fail(c, C2D_E_STATE, "c2d_obs_set_accumulate: the set is empty");
+  if (events && n < 0) return C2D_E_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  c->oset_started = true;
+  if (!events) {
+    const double* seg[C2D_EV_SHARDS];
+    int64_t cnt[C2D_EV_SHARDS];
+    int64_t tot = 0;
+    for (int sh = 0; sh < C2D_EV_SHARDS; sh++) {
+      seg[sh] = c->ev + (size_t)sh * c->ev_cap_sh * C2D_EVENT_WORDS;
+      cnt[sh] = c->ev_cnt[sh];
+      tot += cnt[sh];
+    }
+    const char* e = getenv("C2D_OBS_ASYNC");
+    if ((e && e[0] == '0') || tot == 0) return obs_set_launch_sync(c, seg, cnt, C2D_EV_SHARDS);
+    /* on obs_stream, after the step that wrote the events; the next
+     * generation-0 launch waits for ev_obs_b (run_step_body).  One launch
+     * over all shards: a set workgroup stages up to 63 KiB of edges and
+     * rows, which one launch per shard would repeat 32 times */
+    HIPCHK(c, hipEventRecord(c->ev_obs_src, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->obs_stream, c->ev_obs_src, 0));
+    HIPCHK(c, hipEventRecord(c->ev_obs_a, c->obs_stream));
+    const int rc = c2d_launch_obs_set(&c->oset, seg, cnt, C2D_EV_SHARDS, obs_set_grid(c, tot), c->obs_stream);
+    if (rc) return fail(c, C2D_E_HIP, "obs set launch: %s", hipGetErrorString((hipError_t)rc));
+    HIPCHK(c, hipEventRecord(c->ev_obs_b, c->obs_stream));
+    c->obs_inflight = true;
+    c->obs_inflight_set = true;
+    c->oset_launches++;
+    return C2D_OK;
+  }
+  if (n > c->obs_ev_cap) {
+    if (c->obs_ev) (void)hipFree(c->obs_ev);
+    c->obs_ev = nullptr;
+    c->obs_ev_cap = 0;
+    HIPCHK(c, dalloc(&c->obs_ev, (size_t)n * C2D_EVENT_WORDS));
+    c->obs_ev_cap = n;
+  }
+  if (n) HIPCHK(c, hipMemcpy(c->obs_ev, events, (size_t)n * C2D_EVENT_WORDS * sizeof(double),
+                             hipMemcpyHostToDevice));
+  const double* ev = c->obs_ev;
+  return obs_set_launch_sync(c, &ev, &n, 1);
+}
+
+extern "C" int c2d_obs_set_accumulate_device(c2d_ctx* c, const double* d_events, int64_t n) {
+  if (!c || !d_events || n < 0) return C2D_E_ARG;
+  if (c->oset.n < 1) return fail(c, C2D_E_STATE, "c2d_obs_set_accumulate_device: the set is empty");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  c->oset_started = true;
+  return obs_set_launch_sync(c, &d_events, &n, 1);
+}
+
+extern "C" int c2d_obs_set_shape(c2d_ctx* c, int32_t id, int32_t* n_t, int32_t* n_mu, int32_t* n_e,
+                                 int32_t* lds_rows) {
+  if (!c) return C2D_E_ARG;
+  if (id < 0 || id >= c->oset.n) return fail(c, C2D_E_ARG, "c2d_obs_set_shape: no member %d", (int)id);
+  const ObsSetMember& M = c->oset.m[id];
+  if (n_t) *n_t = M.n_t;
+  if (n_mu) *n_mu = M.n_mu;
+  if (n_e) *n_e = M.n_e;
+  if (lds_rows) *lds_rows = M.lds_rows;
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_result(c2d_ctx* c, int32_t id, double* F, double* F2, double* count) {
+  if (!c) return C2D_E_ARG;
+  if (id < 0 || id >= c->oset.n) return fail(c, C2D_E_ARG, "c2d_obs_set_result: no member %d", (int)id);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  const ObsSetMember& M = c->oset.m[id];
+  const size_t nh = (size_t)M.n_t * M.n_mu * M.n_e;
+  if (F) HIPCHK(c, hipMemcpy(F, M.F, nh * sizeof(double), hipMemcpyDeviceToHost));
+  if (F2) HIPCHK(c, hipMemcpy(F2, M.F2, nh * sizeof(double), hipMemcpyDeviceToHost));
+  if (count) HIPCHK(c, hipMemcpy(count, M.cnt, nh * sizeof(double), hipMemcpyDeviceToHost));
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_kernel_ms(c2d_ctx* c, double* ms, int32_t* launches) {
+  if (!c) return C2D_E_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  if (ms) *ms = c->oset_ms;
+  if (launches) *launches = c->oset_launches;
+  return C2D_OK;
+}
+
+/* the tool's files of one deck member from its histogram so far; world_sum:
+ * summed over the context's communicator first (every rank calls, rank 0
+ * writes) */
+extern "C" int c2d_obs_set_write(c2d_ctx* c, int32_t id, const char* path, int32_t factor, int32_t world_sum) {
+  if (!c) return C2D_E_ARG;
+  if (id < 0 || id >= c->oset.n) return fail(c, C2D_E_ARG, "c2d_obs_set_write: no member %d", (int)id);
+  const ObsSetHost& H = c->oset_h[(size_t)id];
+  if (!H.kind) return fail(c, C2D_E_STATE, "c2d_obs_set_write: member %d was added without a deck", (int)id);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  const ObsSetMember& M = c->oset.m[id];
+  const size_t nh = (size_t)M.n_t * M.n_mu * M.n_e;
+  std::vector<double> h(3 * nh);
+  if (world_sum) {
+    if (!c->comm) return fail(c, C2D_E_STATE, "c2d_obs_set_write: world_sum needs c2d_comm_init");
+    double* w = H.red;
+    HIPCHK(c, hipMemcpyAsync(w, H.hist, 3 * nh * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    const ncclResult_t r = ncclAllReduce(w, w, 3 * nh, ncclDouble, ncclSum, c->comm, c->stream);
+    if (r != ncclSuccess) return fail(c, C2D_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
+    HIPCHK(c, hipMemcpyAsync(h.data(), w, 3 * nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->comm_rank != 0) return C2D_OK;
+  } else {
+    HIPCHK(c, hipMemcpy(h.data(), H.hist, 3 * nh * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  const double *F = h.data(), *F2 = F + nh, *cnt = F2 + nh;
+  if (H.kind == 1) {
+    const char* out = (path && path[0]) ? path : H.pspt.outfile;
+    if (c2d_pspt_write(out, &H.pspt, F, cnt, factor))
+      return fail(c, C2D_E_IO, "c2d_obs_set_write: cannot write '%s'", out);
+  } else {
+    const char* dir = (path && path[0]) ? path : ".";
+    if (c2d_plcm_write(dir, &H.plcm[0], F, F2, cnt, factor))
+      return fail(c, C2D_E_IO, "c2d_obs_set_write: cannot write the light-curve files under '%s'", dir);
+  }
   return C2D_OK;
 }
 

@@ -16,6 +16,10 @@
  * later rows use wave-aggregated global atomics (one atomic per distinct bin
  * per wave), so hot bins never serialise lane by lane.  The event stream is
  * read once: 56 B per event (HBM-bound).
+ *
+ * c2d_obs_set_kernel fills several such histograms (an observer set: SEDs of
+ * several windows and light curves, c2d_obs_set_*) in one pass: the event
+ * words and cos(phi) are shared, the members share the workgroup's LDS.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -175,7 +179,149 @@ __global__ void __launch_bounds__(OBS_BLOCK) c2d_obs_kernel(const ObsDev O, cons
   }
 }
 
+/* An observer set: up to OBS_SET_MAX binnings (SEDs and light curves, each
+ * with its own Gamma, r_max, t_offset and edges) filled in one pass over the
+ * events.  Per event, once: the segment lookup, the 7 words and c2d_cos(phi).
+ * Per member, in a wave-uniform loop: the boost, the bin search and the
+ * accumulation of c2d_obs_kernel, operation for operation, so a member's
+ * bin decisions are those of the single-observer kernel.
+ *
+ * LDS (planned on the host, capi.cpp obs_set_plan; never more than
+ * OBS_SET_LDS with the static tables): the edges of every member, then each
+ * member's leading lds_rows time rows privatised (F, F2, count); later rows
+ * go through agg_add to global memory. */
+__global__ void __launch_bounds__(OBS_BLOCK) c2d_obs_set_kernel(const ObsSetDev Q, const ObsSegs S) {
+  __shared__ int64_t seg_pre[C2D_EV_SHARDS + 1];
+  __shared__ const double* seg_base[C2D_EV_SHARDS];
+  __shared__ double betta_m[OBS_SET_MAX];
+  if (threadIdx.x <= (unsigned)S.nseg) seg_pre[threadIdx.x] = S.pre[threadIdx.x];
+  if (threadIdx.x < (unsigned)S.nseg) seg_base[threadIdx.x] = S.base[threadIdx.x];
+  if (threadIdx.x < (unsigned)Q.n) {
+    const double G = Q.m[threadIdx.x].gam_bulk;
+    betta_m[threadIdx.x] = __builtin_sqrt(1. - 1. / (G * G));
+  }
+  const int64_t n = S.pre[S.nseg];
+  extern __shared__ double sh[];
+  for (int i = threadIdx.x; i < Q.n_edges; i += OBS_BLOCK) sh[i] = Q.edges[i];
+  for (int i = threadIdx.x; i < Q.n_hist; i += OBS_BLOCK) sh[Q.n_edges + i] = 0.0;
+  __syncthreads();
+  /* wave-uniform trip counts (events, members, bands): every lane reaches agg_add */
+  for (int64_t base = (int64_t)blockIdx.x * OBS_BLOCK; base < n; base += (int64_t)gridDim.x * OBS_BLOCK) {
+    const int64_t e = base + threadIdx.x;
+    const bool valid = e < n;
+    const int64_t ee = valid ? e : 0;
+    int sg = 0;                            /* last segment with seg_pre[sg] <= ee */
+    for (int hi = S.nseg - 1; sg < hi;) {
+      const int m = (sg + hi + 1) >> 1;
+      if (seg_pre[m] <= ee) sg = m; else hi = m - 1;
+    }
+    const double* v = seg_base[sg] + (ee - seg_pre[sg]) * C2D_EVENT_WORDS;
+    const double tb0 = v[0], En0 = v[1], ew0 = v[2];
+    const double r = v[3], z = v[4];
+    const double mu_c = -v[5];
+    const double rcos = r * c2d_cos(v[6]);
+    for (int j = 0; j < Q.n; j++) {
+      const ObsSetMember& M = Q.m[j];
+      const double* t0 = sh + M.edge_off;
+      const double* t1 = t0 + M.n_t;
+      const double* mu0 = t1 + M.n_t;
+      const double* mu1 = mu0 + M.n_mu;
+      const double* E0 = mu1 + M.n_mu;
+      const double* E1 = E0 + M.n_e;
+      const int nl = M.lds_rows * M.n_mu * M.n_e;
+      double* hF = sh + M.hist_off;
+      double* hF2 = hF + nl;
+      double* hC = hF2 + nl;
+      auto add = [&](int h, double w) {
+        if (h >= 0 && h < nl) {
+          atomicAdd(&hF[h], w);
+          atomicAdd(&hF2[h], w * w);
+          atomicAdd(&hC[h], 1.0);
+        }
+        agg_add(M.F, M.F2, M.cnt, h >= nl ? h : -1, w);
+      };
+      /* pspt.c:253-272 / plcm.c:390-399, as c2d_obs_kernel */
+      const double G = M.gam_bulk;
+      const double betta = betta_m[j];
+      double mu = mu_c;
+      const double doppler = G * (1. + mu * betta);
+      const double t_bound = (tb0 - betta * z * 3.33333333e-11) / doppler;
+      const double E = En0 * doppler;
+      const double ew = ew0 * doppler;
+      mu = (mu + betta) / (1. + mu * betta);
+      const double cdt = z * mu / G + __builtin_sqrt(1. - mu * mu) * (M.rmax - rcos);
+      double time = t_bound + 3.33333333e-11 * cdt;
+      if (M.mode == C2D_OBS_SED) {
+        int h = -1;
+        if (valid && !(mu < mu0[0] || mu > mu1[0])) {
+          const int k = first_bin(E0, E1, M.n_e, M.sorted_e, E);
+          const int m = first_bin(t0, t1, M.n_t, M.sorted_t, time);
+          if (k < M.n_e && m < M.n_t) h = m * M.n_e + k;
+        }
+        add(h, ew);
+      } else {
+        time -= M.t_offset;
+        int row = -1;
+        if (valid && !(time < 0.)) {
+          const int k = first_bin(t0, t1, M.n_t, M.sorted_t, time);
+          const int m = first_bin(mu0, mu1, M.n_mu, M.sorted_mu, mu);
+          if (k < M.n_t && m < M.n_mu) row = (k * M.n_mu + m) * M.n_e;
+        }
+        for (int l = 0; l < M.n_e; l++)                          /* every band containing E */
+          add((row >= 0 && E >= E0[l] && E < E1[l]) ? row + l : -1, ew);
+      }
+    }
+  }
+  if (Q.n_hist) {
+    __syncthreads();
+    for (int j = 0; j < Q.n; j++) {
+      const ObsSetMember& M = Q.m[j];
+      const int nl = M.lds_rows * M.n_mu * M.n_e;
+      const double* hF = sh + M.hist_off;
+      const double* hF2 = hF + nl;
+      const double* hC = hF2 + nl;
+      for (int i = threadIdx.x; i < nl; i += OBS_BLOCK) {
+        if (hC[i] != 0.0) {
+          atomicAdd(&M.F[i], hF[i]);
+          atomicAdd(&M.F2[i], hF2[i]);
+          atomicAdd(&M.cnt[i], hC[i]);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace c2d
+
+/* one launch of the set kernel over nseg event segments; lds_bytes is the
+ * plan's dynamic LDS (edges + privatised rows) */
+extern "C" int c2d_launch_obs_set(const c2d::ObsSetDev* Q, const double* const* ev, const int64_t* n, int nseg,
+                                  int grid, hipStream_t stream) {
+  if (nseg < 1 || nseg > C2D_EV_SHARDS || Q->n < 1 || Q->n > c2d::OBS_SET_MAX) return (int)hipErrorInvalidValue;
+  const size_t lds = sizeof(double) * ((size_t)Q->n_edges + (size_t)Q->n_hist);
+  if (lds + c2d::OBS_SET_LDS_STATIC > (size_t)c2d::OBS_SET_LDS) return (int)hipErrorInvalidValue;
+  for (int j = 0; j < Q->n; j++) {           /* every member's LDS ranges lie inside the allocation */
+    const c2d::ObsSetMember& M = Q->m[j];
+    if (M.n_t < 1 || M.n_mu < 1 || M.n_e < 1 || M.lds_rows < 0 || M.lds_rows > M.n_t) return (int)hipErrorInvalidValue;
+    const int64_t ne = 2 * ((int64_t)M.n_t + M.n_mu + M.n_e), nl = (int64_t)M.lds_rows * M.n_mu * M.n_e;
+    if (M.edge_off < 0 || M.edge_off + ne > Q->n_edges || M.hist_off < Q->n_edges ||
+        M.hist_off + 3 * nl > (int64_t)Q->n_edges + Q->n_hist)
+      return (int)hipErrorInvalidValue;
+  }
+  c2d::ObsSegs S;
+  int k = 0;
+  S.pre[0] = 0;
+  for (int s = 0; s < nseg; s++) {
+    if (n[s] <= 0) continue;
+    S.base[k] = ev[s];
+    S.pre[k + 1] = S.pre[k] + n[s];
+    k++;
+  }
+  if (k == 0) return 0;
+  S.nseg = k;
+  hipLaunchKernelGGL(c2d::c2d_obs_set_kernel, dim3(grid), dim3(c2d::OBS_BLOCK), lds, stream, *Q, S);
+  return (int)hipGetLastError();
+}
 
 extern "C" size_t c2d_obs_lds_bytes(int n_t, int n_mu, int n_e, int lds_rows) {
   return sizeof(double) * (2 * (size_t)(n_t + n_mu + n_e) + 3 * (size_t)lds_rows * n_mu * n_e);

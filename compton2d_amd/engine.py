@@ -140,6 +140,26 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_obs_begin_pspt.argtypes = [vp, C.c_char_p]
     lib.c2d_obs_write_pspt.restype = C.c_int
     lib.c2d_obs_write_pspt.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32]
+    pi32 = C.POINTER(C.c_int32)
+    lib.c2d_obs_set_clear.restype = C.c_int
+    lib.c2d_obs_set_clear.argtypes = [vp]
+    lib.c2d_obs_set_add.restype = C.c_int
+    lib.c2d_obs_set_add.argtypes = [vp, C.POINTER(abi.ObsBins), pi32]
+    for fn in ("c2d_obs_set_add_pspt", "c2d_obs_set_add_plcm"):
+        getattr(lib, fn).restype = C.c_int
+        getattr(lib, fn).argtypes = [vp, C.c_char_p, pi32]
+    lib.c2d_obs_set_accumulate.restype = C.c_int
+    lib.c2d_obs_set_accumulate.argtypes = [vp, C.POINTER(C.c_double), C.c_int64]
+    lib.c2d_obs_set_accumulate_device.restype = C.c_int
+    lib.c2d_obs_set_accumulate_device.argtypes = [vp, C.c_void_p, C.c_int64]
+    lib.c2d_obs_set_shape.restype = C.c_int
+    lib.c2d_obs_set_shape.argtypes = [vp, C.c_int32] + [pi32] * 4
+    lib.c2d_obs_set_result.restype = C.c_int
+    lib.c2d_obs_set_result.argtypes = [vp, C.c_int32] + [C.POINTER(C.c_double)] * 3
+    lib.c2d_obs_set_kernel_ms.restype = C.c_int
+    lib.c2d_obs_set_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), pi32]
+    lib.c2d_obs_set_write.restype = C.c_int
+    lib.c2d_obs_set_write.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int32, C.c_int32]
     lib.c2d_electron_state.restype = C.c_int
     lib.c2d_electron_state.argtypes = [vp, abi.MArray3, abi.MArray3]
     lib.c2d_comm_unique_id.restype = C.c_int
@@ -477,6 +497,69 @@ class Engine:
     def obs_write_pspt(self, path: str = "", factor: int = 0, world_sum: bool = False) -> None:
         """Write pspt's output file from the histogram so far (c2d_obs_write_pspt)."""
         self._check(self.lib.c2d_obs_write_pspt(self.ctx, str(path).encode(), int(factor), int(world_sum)))
+
+    # -- observer sets: several binnings in one pass over the events ----------
+    def obs_set_clear(self) -> None:
+        """Drop every member of the observer set (c2d_obs_set_clear)."""
+        self._check(self.lib.c2d_obs_set_clear(self.ctx))
+
+    def obs_set_add(self, binning) -> int:
+        """Add `binning` (observer.Binning) with a zeroed histogram; its id."""
+        i = C.c_int32(-1)
+        self._check(self.lib.c2d_obs_set_add(self.ctx, C.byref(binning.to_ctypes()), C.byref(i)))
+        return i.value
+
+    def obs_set_add_pspt(self, deck: str = "") -> int:
+        """Add the SED binning of pspt's input dialogue `deck`; its id."""
+        i = C.c_int32(-1)
+        self._check(self.lib.c2d_obs_set_add_pspt(self.ctx, deck.encode(), C.byref(i)))
+        return i.value
+
+    def obs_set_add_plcm(self, deck: str = "") -> int:
+        """Add the light-curve binning of plcm's input dialogue `deck`; its id."""
+        i = C.c_int32(-1)
+        self._check(self.lib.c2d_obs_set_add_plcm(self.ctx, deck.encode(), C.byref(i)))
+        return i.value
+
+    def obs_set_accumulate(self, events=None) -> None:
+        """Bin host events [n, 7] into every member in one pass, or with None
+        the last transport step's device event buffer."""
+        if events is None:
+            self._check(self.lib.c2d_obs_set_accumulate(self.ctx, None, 0))
+            return
+        ev = np.ascontiguousarray(events, np.float64).reshape(-1, abi.EVENT_WORDS)
+        self._check(self.lib.c2d_obs_set_accumulate(self.ctx, ev.ctypes.data_as(abi.PD), len(ev)))
+
+    def obs_set_accumulate_device(self, ptr: int, n: int) -> None:
+        """Bin n events at device address `ptr` into every member."""
+        self._check(self.lib.c2d_obs_set_accumulate_device(self.ctx, C.c_void_p(ptr), n))
+
+    def obs_set_shape(self, member: int):
+        """(n_t, n_mu, n_e, lds_rows) of a member: its histogram shape and
+        the leading time rows the kernel keeps in LDS."""
+        v = [C.c_int32() for _ in range(4)]
+        self._check(self.lib.c2d_obs_set_shape(self.ctx, int(member), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def obs_set_result(self, member: int):
+        """Raw sums (F, F2, count) of a member, each [n_t, n_mu, n_e]."""
+        shape = self.obs_set_shape(member)[:3]
+        F, F2, cnt = (np.zeros(shape) for _ in range(3))
+        self._check(self.lib.c2d_obs_set_result(self.ctx, int(member), F.ctypes.data_as(abi.PD),
+                                                F2.ctypes.data_as(abi.PD), cnt.ctypes.data_as(abi.PD)))
+        return F, F2, cnt
+
+    def obs_set_kernel_ms(self):
+        """Device milliseconds and number of the set's kernel launches so far."""
+        ms, n = C.c_double(), C.c_int32()
+        self._check(self.lib.c2d_obs_set_kernel_ms(self.ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def obs_set_write(self, member: int, path: str = "", factor: int = 0, world_sum: bool = False) -> None:
+        """The tool's files of a deck member: `path` is pspt's output file, or
+        the directory of plcm's files ("" = the deck's name / ".")."""
+        self._check(self.lib.c2d_obs_set_write(self.ctx, int(member), str(path).encode(), int(factor),
+                                               int(world_sum)))
 
     def fp_tridag(self, a, b, c, r, x0=None) -> np.ndarray:
         """Batched tridag (src/update2d.f:2476-2518); arrays [ncell, nt]."""

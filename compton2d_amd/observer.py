@@ -20,6 +20,11 @@ formats (`write_sed`, `write_lc`).
 
     python -m compton2d_amd.observer pspt < mrk421_sed.input   # in the run dir
     python -m compton2d_amd.observer plcm < mrk421_lc.input
+
+Several decks over the same event files are binned in one pass per file (the
+observer set, c2d_obs_set_*: `bin_events_set`, `run_tools`):
+
+    python -m compton2d_amd.observer multi --pspt mrk421_sed.input --plcm mrk421_lc.input
 """
 from __future__ import annotations
 
@@ -340,6 +345,20 @@ def bin_events(engine, binning: Binning, events: Iterable[Optional[np.ndarray]])
     return Histogram(F, F2, cnt, ms)
 
 
+def bin_events_set(engine, binnings: Sequence[Binning],
+                   events: Iterable[Optional[np.ndarray]]) -> List[Histogram]:
+    """Histogram event batches into every binning of `binnings` in one pass
+    over each batch (the engine's observer set, c2d_obs_set_*; None = the
+    device event buffer of the last transport step).  kernel_ms is the set's
+    device time, the same on every histogram."""
+    engine.obs_set_clear()
+    ids = [engine.obs_set_add(b) for b in binnings]
+    for ev in events:
+        engine.obs_set_accumulate(ev)
+    ms, _ = engine.obs_set_kernel_ms()
+    return [Histogram(*engine.obs_set_result(i), ms) for i in ids]
+
+
 # ---------------------------------------------------------------------------
 # normalisation and output (the tools' formats)
 # ---------------------------------------------------------------------------
@@ -473,10 +492,57 @@ def run_tool(tool: str, deck: str, directory=".", device: int = 0) -> List[Path]
     return write_lc(d, b, h, factor)
 
 
+def run_tools(tools: Sequence[Tuple[str, str]], directory=".", device: int = 0) -> List[Path]:
+    """Run several (tool, deck) dialogues over the event files in `directory`:
+    every event file is read once and binned into every deck that names its
+    series in one pass on GPU `device` (the observer set); write each tool's
+    output files.  Decks that write the same file names overwrite each other,
+    as the tools run one after another would."""
+    from .engine import obs_engine
+    bins = [parse_pspt_deck(deck) if tool == "pspt" else parse_plcm_deck(deck) for tool, deck in tools]
+    series: dict = {}
+    for i, b in enumerate(bins):
+        series.setdefault(b.infile, []).append(i)
+    d = Path(directory)
+    written: List[Path] = []
+    eng = obs_engine(device)
+    try:
+        for infile, members in series.items():
+            files, factor = event_files(infile, directory)
+            hs = bin_events_set(eng, [bins[i] for i in members], (read_events(f) for f in files))
+            for i, h in zip(members, hs):
+                if tools[i][0] == "pspt":
+                    write_sed(d / bins[i].outfiles[0], bins[i], h, factor)
+                    written.append(d / bins[i].outfiles[0])
+                else:
+                    written += write_lc(d, bins[i], h, factor)
+    finally:
+        eng.close()
+    return written
+
+
+_USAGE = ("usage: python -m compton2d_amd.observer {pspt|plcm} < deck\n"
+          "       python -m compton2d_amd.observer multi [--dir RUNDIR] {--pspt|--plcm} DECKFILE ...")
+
+
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else argv
+    if argv and argv[0] == "multi":
+        tools, directory, a = [], ".", argv[1:]
+        while len(a) >= 2 and a[0] in ("--pspt", "--plcm", "--dir"):
+            if a[0] == "--dir":
+                directory = a[1]
+            else:
+                tools.append((a[0][2:], Path(a[1]).read_text()))
+            a = a[2:]
+        if a or not tools:
+            print(_USAGE, file=sys.stderr)
+            return 2
+        for p in run_tools(tools, directory):
+            print(p)
+        return 0
     if not argv or argv[0] not in ("pspt", "plcm"):
-        print("usage: python -m compton2d_amd.observer {pspt|plcm} < deck", file=sys.stderr)
+        print(_USAGE, file=sys.stderr)
         return 2
     for p in run_tool(argv[0], sys.stdin.read()):
         print(p)

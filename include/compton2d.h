@@ -498,6 +498,54 @@ int  c2d_obs_begin_pspt(c2d_ctx* ctx, const char* deck);
  * calls, rank 0 writes). */
 int  c2d_obs_write_pspt(c2d_ctx* ctx, const char* path, int32_t factor, int32_t world_sum);
 
+/* Observer sets: up to C2D_OBS_SET_MAX binnings (pspt SEDs of several
+ * windows, plcm light curves, raw c2d_obs_bins), each with its own Gamma,
+ * r_max, t_offset and edges, filled by ONE pass over the escape events: an
+ * accumulate call reads the events once and launches the same number of
+ * kernels however many members the set has.  The set's state is separate
+ * from the single histogram of c2d_obs_begin; both may be used after the
+ * same step (each waits for the other's binning of the device event buffer).
+ * The edges of all members are staged in one workgroup's LDS (63 KiB):
+ * an add that would exceed it fails with C2D_E_ARG and leaves the set as it
+ * was.  Members are numbered from 0 in the order they are added. */
+#define C2D_OBS_SET_MAX 8
+/* Drop every member (and its histogram). */
+int  c2d_obs_set_clear(c2d_ctx* ctx);
+/* Add a member with a zeroed histogram; *id (may be NULL) receives its
+ * number.  Arguments and limits as c2d_obs_begin; a ninth member is
+ * C2D_E_ARG; adding after the first accumulate since c2d_obs_set_clear is
+ * C2D_E_STATE. */
+int  c2d_obs_set_add(c2d_ctx* ctx, const c2d_obs_bins* bins, int32_t* id);
+/* Add a member from pspt's dialogue (as c2d_obs_begin_pspt) or from plcm's
+ * (postprocessing/plcm.c:97-302, e.g. postprocessing/mrk421_lc.input: names,
+ * angular bins, dt, t_offset, t_max, energy bands; plcm's 1024 chained time
+ * bins). */
+int  c2d_obs_set_add_pspt(c2d_ctx* ctx, const char* deck, int32_t* id);
+int  c2d_obs_set_add_plcm(c2d_ctx* ctx, const char* deck, int32_t* id);
+/* Bin events into every member: events == NULL bins the last transport
+ * step's device event buffer (asynchronously, like c2d_obs_accumulate: the
+ * next step's first launch and every reader wait for it), otherwise n host
+ * events of 7 f64.  C2D_E_STATE on an empty set. */
+int  c2d_obs_set_accumulate(c2d_ctx* ctx, const double* events, int64_t n);
+/* Same for n events already in device memory on the context's GPU. */
+int  c2d_obs_set_accumulate_device(c2d_ctx* ctx, const double* d_events, int64_t n);
+/* A member's histogram shape and how many of its leading time rows the
+ * kernel keeps in LDS (the rest use global atomics); any pointer may be NULL. */
+int  c2d_obs_set_shape(c2d_ctx* ctx, int32_t id, int32_t* n_t, int32_t* n_mu, int32_t* n_e, int32_t* lds_rows);
+/* Download a member's raw sums ([n_t][n_mu][n_e] each; any may be NULL). */
+int  c2d_obs_set_result(c2d_ctx* ctx, int32_t id, double* F, double* F2, double* count);
+/* Device time (ms) and number of the set's kernel launches since the clear. */
+int  c2d_obs_set_kernel_ms(c2d_ctx* ctx, double* ms, int32_t* launches);
+/* Write the tool's files of a deck member from its histogram so far
+ * (C2D_E_STATE for a member added with raw bins).  pspt member: `path` is
+ * the output file (NULL/"" = the deck's name), as c2d_obs_write_pspt.  plcm
+ * member: `path` is a directory (NULL/"" = "."); the files take the deck's
+ * names: <name> and <name>_aux per angular bin and one <name>_particles
+ * (plcm.c:377-388, 466-552).  world_sum != 0: F, F2 and count of the member
+ * are summed over the context's communicator first (every rank calls, rank
+ * 0 writes). */
+int  c2d_obs_set_write(c2d_ctx* ctx, int32_t id, const char* path, int32_t factor, int32_t world_sum);
+
 /* Copy the context's device electron state (C2D_DEV_ELECTRONS) into the
  * caller's f_nt / Pnt views (either may have NULL data), e.g. before
  * write_record (src/write_record.f) in a device-resident run. */

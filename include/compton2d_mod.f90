@@ -140,6 +140,7 @@ module compton2d
 
   ! ---- observer-frame binning (c2d_obs_*; postprocessing/pspt.c, plcm.c) ----
   integer, parameter :: C2D_OBS_SED = 0, C2D_OBS_LC = 1
+  integer, parameter :: C2D_OBS_SET_MAX = 8     ! members of an observer set (c2d_obs_set_*)
 
   type, bind(C) :: c2d_obs_bins
      integer(c_int32_t) :: mode = 0
@@ -322,6 +323,81 @@ module compton2d
        character(kind=c_char), intent(in) :: path(*)
        integer(c_int32_t), value :: factor, world_sum
      end function c2d_obs_write_pspt
+
+     ! ---- observer sets: up to C2D_OBS_SET_MAX binnings filled in one pass
+     !      over the escapes (several pspt SEDs and plcm light curves) ----
+     integer(c_int) function c2d_obs_set_clear(ctx) bind(C, name='c2d_obs_set_clear')
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+     end function c2d_obs_set_clear
+
+     integer(c_int) function c2d_obs_set_add(ctx, bins, id) bind(C, name='c2d_obs_set_add')
+       import :: c_int, c_ptr, c_int32_t, c2d_obs_bins
+       type(c_ptr), value :: ctx
+       type(c2d_obs_bins), intent(in) :: bins
+       integer(c_int32_t), intent(out) :: id           ! the member's number, from 0
+     end function c2d_obs_set_add
+
+     ! pspt's / plcm's dialogue (one answer a line, NUL-terminated) -> a member
+     integer(c_int) function c2d_obs_set_add_pspt(ctx, deck, id) bind(C, name='c2d_obs_set_add_pspt')
+       import :: c_int, c_ptr, c_char, c_int32_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: deck(*)
+       integer(c_int32_t), intent(out) :: id
+     end function c2d_obs_set_add_pspt
+
+     integer(c_int) function c2d_obs_set_add_plcm(ctx, deck, id) bind(C, name='c2d_obs_set_add_plcm')
+       import :: c_int, c_ptr, c_char, c_int32_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: deck(*)
+       integer(c_int32_t), intent(out) :: id
+     end function c2d_obs_set_add_plcm
+
+     integer(c_int) function c2d_obs_set_accumulate(ctx, events, n) bind(C, name='c2d_obs_set_accumulate')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx, events           ! c_null_ptr: device events of the last step
+       integer(c_int64_t), value :: n
+     end function c2d_obs_set_accumulate
+
+     integer(c_int) function c2d_obs_set_accumulate_device(ctx, d_events, n) &
+          bind(C, name='c2d_obs_set_accumulate_device')
+       import :: c_int, c_ptr, c_int64_t
+       type(c_ptr), value :: ctx, d_events         ! device address of n events
+       integer(c_int64_t), value :: n
+     end function c2d_obs_set_accumulate_device
+
+     integer(c_int) function c2d_obs_set_shape(ctx, id, n_t, n_mu, n_e, lds_rows) &
+          bind(C, name='c2d_obs_set_shape')
+       import :: c_int, c_ptr, c_int32_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), value :: id
+       integer(c_int32_t), intent(out) :: n_t, n_mu, n_e, lds_rows
+     end function c2d_obs_set_shape
+
+     integer(c_int) function c2d_obs_set_result(ctx, id, F, F2, cnt) bind(C, name='c2d_obs_set_result')
+       import :: c_int, c_ptr, c_int32_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), value :: id
+       type(c_ptr), value :: F, F2, cnt            ! [n_e, n_mu, n_t] in Fortran order
+     end function c2d_obs_set_result
+
+     integer(c_int) function c2d_obs_set_kernel_ms(ctx, ms, launches) bind(C, name='c2d_obs_set_kernel_ms')
+       import :: c_int, c_ptr, c_double, c_int32_t
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: ms
+       integer(c_int32_t), intent(out) :: launches
+     end function c2d_obs_set_kernel_ms
+
+     ! a deck member's files: path = pspt's output file, or the directory of
+     ! plcm's files (NUL-terminated; empty = the deck's name / ".")
+     integer(c_int) function c2d_obs_set_write(ctx, id, path, factor, world_sum) &
+          bind(C, name='c2d_obs_set_write')
+       import :: c_int, c_ptr, c_char, c_int32_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), value :: id
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int32_t), value :: factor, world_sum
+     end function c2d_obs_set_write
 
      ! ---- RCCL tally all-reduce (replaces xec_add / graphics_collect,
      !      src/xec2d.f:325-399, and cens_add_up / E_add_up,
