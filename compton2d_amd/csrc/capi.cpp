@@ -22,6 +22,7 @@
 #include "c2d_rng.h"
 #include "pspt_host.h"
 #include "plcm_host.h"
+#include "c2d_evtext.hpp"
 
 using namespace c2d;
 
@@ -193,6 +194,9 @@ struct c2d_ctx {
   double* ev = nullptr;
   int64_t n_ev = 0;
   int64_t ev_cnt[C2D_EV_SHARDS] = {};   /* events in each shard of the buffer (last step) */
+  bool ev_stepped = false;              /* a step has filled (or emptied) the event buffer */
+  c2d_evt_writer* evt = nullptr;        /* c2d_events_write's staging buffers (evtext.hip) */
+  c2d_evt_times evt_times = {};         /* of the last c2d_events_write* */
   /* the context's own escapes binned on a second stream (c2d_obs_accumulate
    * with no events): it overlaps the next step's FP / tables / sources, and
    * the next generation-0 launch, which rewrites the event buffer, waits
@@ -523,6 +527,7 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->obs_stream) (void)hipStreamSynchronize(c->obs_stream);   /* it reads the event buffer */
   if (c->mono_flag) (void)hipFree(c->mono_flag);
+  c2d_evtext_free(c->evt);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   void* ptrs[] = {c->geo, c->gnt, c->kappa_cur, c->kappa_prev, c->eps_tot, c->eps_th, c->f_nt,
                   c->Pnt, c->n_e, c->vfrac, c->ewsv, c->surf_ew, c->surf_tbb, c->tbbl,
@@ -1661,6 +1666,7 @@ static int run_step_body(c2d_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(c->T + c->L.counters, hc, sizeof hc, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->n_ev = 0;
+  c->ev_stepped = true;
   unsigned long long ev_reserved = 0;
   for (int sh = 0; sh < C2D_EV_SHARDS; sh++) {
     const unsigned long long m = ctl[CTL_EVSH + sh * C2D_EV_SHARD_STRIDE];
@@ -3239,5 +3245,53 @@ extern "C" int c2d_allreduce_tallies(c2d_ctx* c) {
                                        c->stream);
   if (r != ncclSuccess) return fail(c, C2D_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return C2D_OK;
+}
+
+/* ------------------------------------------------------------------------
+ * Escape events as p###_evb.dat text, formatted on the device (evtext.hip)
+ * ---------------------------------------------------------------------- */
+static_assert(C2D_EVT_MAXSEG == C2D_EV_SHARDS, "the writer takes the event buffer's shards as its segments");
+static int events_write_segments(c2d_ctx* c, const double* const* seg, const int64_t* cnt, int nseg, int on_device,
+                                 const char* path, int32_t append, int64_t* n_written) {
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  /* an asynchronous observer pass reads the same events: let it finish, as
+   * the other readers do (its result and timing are kept) */
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  char err[512] = "";
+  const int rc = c2d_evtext_write(&c->evt, c->cfg.device, c->stream, seg, cnt, nseg, on_device, path, append != 0,
+                                  n_written, &c->evt_times, err, sizeof err);
+  return rc ? fail(c, rc, "%s", err) : C2D_OK;
+}
+
+extern "C" int c2d_events_write(c2d_ctx* c, const char* path, int32_t append, int64_t* n_written) {
+  if (!c || !path || !path[0]) return C2D_E_ARG;
+  if (!c->ev_stepped) return fail(c, C2D_E_STATE, "c2d_events_write: no transport step has run");
+  const double* seg[C2D_EV_SHARDS];
+  int64_t cnt[C2D_EV_SHARDS];
+  for (int sh = 0; sh < C2D_EV_SHARDS; sh++) {   /* the shards' filled prefixes, in shard order (c2d_events) */
+    seg[sh] = c->ev + (size_t)sh * c->ev_cap_sh * C2D_EVENT_WORDS;
+    cnt[sh] = c->ev_cnt[sh];
+  }
+  return events_write_segments(c, seg, cnt, C2D_EV_SHARDS, 1, path, append, n_written);
+}
+
+extern "C" int c2d_events_write_from(c2d_ctx* c, const double* events, int64_t n, int32_t on_device,
+                                     const char* path, int32_t append) {
+  if (!c || !path || !path[0] || n < 0 || (n > 0 && !events)) return C2D_E_ARG;
+  return events_write_segments(c, &events, &n, 1, on_device != 0, path, append, nullptr);
+}
+
+extern "C" int c2d_last_events_write_ms(c2d_ctx* c, double* scan_ms, double* kernel_ms, double* wait_ms,
+                                        double* io_ms, int64_t* ambiguous, int64_t* multilimb,
+                                        int32_t* chunks) {
+  if (!c) return C2D_E_ARG;
+  if (scan_ms) *scan_ms = c->evt_times.scan_ms;
+  if (kernel_ms) *kernel_ms = c->evt_times.kernel_ms;
+  if (wait_ms) *wait_ms = c->evt_times.wait_ms;
+  if (io_ms) *io_ms = c->evt_times.io_ms;
+  if (ambiguous) *ambiguous = c->evt_times.ambiguous;
+  if (multilimb) *multilimb = c->evt_times.multilimb;
+  if (chunks) *chunks = c->evt_times.chunks;
   return C2D_OK;
 }

@@ -74,6 +74,15 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_tally_download_range.argtypes = [vp, C.POINTER(C.c_double), C.c_int64, C.c_int64]
     lib.c2d_events.restype = C.c_int
     lib.c2d_events.argtypes = [vp, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64)]
+    lib.c2d_events_write.restype = C.c_int
+    lib.c2d_events_write.argtypes = [vp, C.c_char_p, C.c_int32, C.POINTER(C.c_int64)]
+    lib.c2d_events_write_from.restype = C.c_int
+    lib.c2d_events_write_from.argtypes = [vp, C.c_void_p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
+    lib.c2d_last_events_write_ms.restype = C.c_int
+    lib.c2d_last_events_write_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int64)] * 2 + [
+        C.POINTER(C.c_int32)]
+    lib.c2d_selftest_fmt.restype = C.c_int
+    lib.c2d_selftest_fmt.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_char_p]
     lib.c2d_census_count.restype = C.c_int
     lib.c2d_census_count.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.c2d_census_export.restype = C.c_int
@@ -455,6 +464,42 @@ class Engine:
         self._check(self.lib.c2d_last_vem_ms(self.ctx, C.byref(ms)))
         return ms.value
 
+    # -- the escape-event file (imcleak2d.f:181), written by the library -----
+    def events_write(self, path, append: bool = False) -> int:
+        """Write the last transport step's escape events to `path` as
+        p###_evb.dat text, formatted on the device (c2d_events_write); returns
+        the records written."""
+        n = C.c_int64()
+        self._check(self.lib.c2d_events_write(self.ctx, os.fsencode(path), int(bool(append)), C.byref(n)))
+        return n.value
+
+    def events_write_from(self, events, path, append: bool = False) -> None:
+        """The same for events [n, 7] of the caller: a numpy array, or a
+        float64 torch tensor on this context's GPU (no copy)."""
+        if hasattr(events, "data_ptr"):
+            t = events
+            if not t.is_cuda:
+                return self.events_write_from(t.numpy(), path, append)
+            assert t.dtype.itemsize == 8 and t.is_floating_point() and t.is_contiguous()
+            assert t.numel() % abi.EVENT_WORDS == 0
+            ptr, n, dev = t.data_ptr(), t.numel() // abi.EVENT_WORDS, 1
+            keep = t
+        else:
+            keep = np.ascontiguousarray(events, np.float64).reshape(-1, abi.EVENT_WORDS)
+            ptr, n, dev = keep.ctypes.data, len(keep), 0
+        self._check(self.lib.c2d_events_write_from(self.ctx, C.c_void_p(ptr if n else None), n, dev,
+                                                   os.fsencode(path), int(bool(append))))
+        del keep
+
+    def last_events_write(self) -> dict:
+        """Timings of the last events_write* (c2d_last_events_write_ms)."""
+        d = [C.c_double() for _ in range(4)]
+        amb, ml, chunks = C.c_int64(), C.c_int64(), C.c_int32()
+        self._check(self.lib.c2d_last_events_write_ms(self.ctx, *[C.byref(v) for v in d], C.byref(amb),
+                                                      C.byref(ml), C.byref(chunks)))
+        return {"scan_ms": d[0].value, "kernel_ms": d[1].value, "wait_ms": d[2].value, "io_ms": d[3].value,
+                "ambiguous": amb.value, "multilimb": ml.value, "chunks": chunks.value}
+
     # -- observer-frame binning (postprocessing/pspt.c, plcm.c) ---------------
     def obs_begin(self, binning) -> None:
         """Zero a device histogram for `binning` (observer.Binning)."""
@@ -635,3 +680,14 @@ def device_math(fn: int, x: np.ndarray, device: int = 0) -> np.ndarray:
     if rc != 0:
         raise C2DError(rc, "c2d_selftest_math failed")
     return y
+
+
+def device_fmt_e14_7(x: np.ndarray, device: int = 0) -> np.ndarray:
+    """Fortran E14.7 of every value of x on the GPU (c2d_selftest_fmt): uint8 [n, 14]."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float64).ravel()
+    out = C.create_string_buffer(14 * x.size + 1)
+    rc = lib.c2d_selftest_fmt(device, x.ctypes.data_as(abi.PD), x.size, out)
+    if rc != 0:
+        raise C2DError(rc, "c2d_selftest_fmt failed")
+    return np.frombuffer(out.raw[:14 * x.size], np.uint8).reshape(-1, 14)

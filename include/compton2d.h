@@ -12,7 +12,7 @@
  *   src/imcredist.f:5    imcredist (census bal.)   not needed: census stays on its GPU
  *   src/xec2d.f:325/371  xec_add/graphics_collect  c2d_tally_device_ptr + one all-reduce
  *   src/update2d.f:1929  cens_add_up (REDUCE)      c2d_tally_device_ptr + one all-reduce
- *   src/imcleak2d.f:171  event-file writes         c2d_events
+ *   src/imcleak2d.f:171  event-file writes         c2d_events, c2d_events_write
  *   src/census2d.f:1-76  write_cens/read_cens      c2d_census_export / c2d_census_import
  *   src/update2d.f:7     update (FP_calc, tridag,  c2d_fp_set_config + c2d_fp_step
  *     E_add_up, FP_send_job/recv_result)
@@ -395,6 +395,32 @@ int  c2d_tally_download_range(c2d_ctx* ctx, double* host, int64_t offset, int64_
 
 /* Escape events of the last step: copies min(cap, n) records. */
 int  c2d_events(c2d_ctx* ctx, double* buf, int64_t cap, int64_t* n);
+/* The last step's escape events as p###_evb.dat text (imcleak2d.f:181),
+ * formatted on the device; append != 0 adds to an existing file as the
+ * reference's per-step writes do.  *n_written = records written (n_written
+ * may be NULL).  The events are those of c2d_events, in its order; the call
+ * returns when the file is complete and closed, waits for an asynchronous
+ * observer pass over the same events and changes neither the event buffer
+ * nor the observer state.  Errors: C2D_E_STATE before the first step;
+ * C2D_E_IO if the file cannot be opened or written; C2D_E_NONFINITE if an
+ * event holds a NaN or Inf (the message names the first such record): the
+ * events are scanned before the file is opened, so the file is then exactly
+ * as it was.  No events: an empty file (append == 0) or an untouched one.
+ * The text is staged in chunks of C2D_EVTEXT_CHUNK events (environment, read
+ * at every call; default 1048576) through two pinned host buffers: memory is
+ * bounded by the chunk, not by the event count. */
+int  c2d_events_write(c2d_ctx* ctx, const char* path, int32_t append, int64_t* n_written);
+/* The same for n caller-supplied events (7 f64 each), on the host or
+ * (on_device != 0) in device memory on this context's GPU. */
+int  c2d_events_write_from(c2d_ctx* ctx, const double* events, int64_t n, int32_t on_device,
+                           const char* path, int32_t append);
+/* Diagnostics of the last c2d_events_write*: milliseconds of the non-finite
+ * scan and of the formatting kernels (device time), host time spent waiting
+ * for chunks and in fwrite, the values the kernel's fast path could not
+ * decide (exact ties, round values), those of them that went through the
+ * multi-limb path, and the chunk count.  Any pointer may be NULL. */
+int  c2d_last_events_write_ms(c2d_ctx* ctx, double* scan_ms, double* kernel_ms, double* wait_ms,
+                              double* io_ms, int64_t* ambiguous, int64_t* multilimb, int32_t* chunks);
 
 /* Census held on the device for the next step. */
 int  c2d_census_count(c2d_ctx* ctx, int64_t* n);
@@ -624,6 +650,12 @@ int  c2d_selftest_geom(int device, int nr, const double* in, double* out, int64_
  * answered, shader cycles of the table's gamma_bar and of the series,
  * gamma_bar = K3/K2 - 1/z as the fast kernel forms it from the table). */
 int  c2d_selftest_mcd_fast(int device, const double* z, int n, double* out);
+/* Diagnostics: Fortran E14.7 of n doubles on the GPU (csrc/c2d_fmt.h as the
+ * event writer runs it), 14 bytes each at out + 14 i, no terminator.
+ * C2D_E_NONFINITE if a value is NaN or Inf (its 14 bytes are then '#').
+ * C2D_FMT_SELFTEST_MULTILIMB=1 (environment, read at every call) sends every
+ * value the fast path cannot decide through the multi-limb path. */
+int  c2d_selftest_fmt(int device, const double* x, int64_t n, char* out);
 
 #ifdef __cplusplus
 }

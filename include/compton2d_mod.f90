@@ -228,6 +228,29 @@ module compton2d
        integer(c_int64_t), intent(out) :: n
      end function c2d_events
 
+     ! the last step's escape events as p###_evb.dat text (imcleak2d.f:181),
+     ! formatted on the device; path NUL-terminated; append /= 0 adds to the file
+     integer(c_int) function c2d_events_write(ctx, path, append, n_written) &
+          bind(C, name='c2d_events_write')
+       import :: c_int, c_ptr, c_char, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int32_t), value :: append
+       integer(c_int64_t), intent(out) :: n_written
+     end function c2d_events_write
+
+     ! the same for n caller-supplied events: c_loc of a host array
+     ! (on_device = 0) or a device address (on_device /= 0)
+     integer(c_int) function c2d_events_write_from(ctx, events, n, on_device, path, append) &
+          bind(C, name='c2d_events_write_from')
+       import :: c_int, c_ptr, c_char, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx, events
+       integer(c_int64_t), value :: n
+       integer(c_int32_t), value :: on_device
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int32_t), value :: append
+     end function c2d_events_write_from
+
      integer(c_int) function c2d_census_count(ctx, n) bind(C, name='c2d_census_count')
        import :: c_int, c_ptr, c_int64_t
        type(c_ptr), value :: ctx

@@ -19,6 +19,8 @@
 #   fppmc          rocprofv3 kernel trace + SQ counters of that FP run (memo on)
 #   fpprof         FP section timers off the clamp (sweep build "fpprof", tools/fp_prof.py)
 #   trprof[:t,..]  wave section timers of the C3 run (sweep builds, default "prof"; tools/tr_prof.py)
+#   evtext         the escape-event file: c2d_events_write_from against the host routes
+#                  (tools/evtext_bench.py; EVENTS, REPS)
 #   n2             rehearse bench.py's N>1 path: 2 gloo ranks on device 0 vs 1 rank
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -110,6 +112,9 @@ for r in "$@"; do
         C2D_LIBRARY=$PWD/compton2d_amd/sweep/$t/libcompton2d.so run 300 "trprof_$t" python tools/tr_prof.py --steps ${STEPS}
         tail -2 "$O/trprof_$t.out"
       done ;;
+    evtext)
+      run 600 evtext python tools/evtext_bench.py --events "${EVENTS:-11000000}" --reps "${REPS:-7}"
+      tail -1 "$O/evtext.out" | cut -c1-400 ;;
     n2)
       run 300 n2_w1 python -u bench.py --workload c3 --sources 40000000 --steps 3 --warmup 2 --no-cpu-baseline
       C2D_ONE_GPU=1 C2D_DIST_BACKEND=gloo run 300 n2_w2 python -u -m torch.distributed.run --nnodes=1 \
