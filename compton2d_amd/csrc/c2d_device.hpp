@@ -148,6 +148,15 @@ struct TallyOff {
 #define C2D_TR_BLOCK 256
 #endif
 #define C2D_EV_SHARD_STRIDE 16
+/* The bundle kernel's per-wave escape queue (KParams.evq_cap): a lane whose
+ * recombined copy leaves the grid stores what imcleak needs (C2D_EVQ_WORDS
+ * doubles) in the wave's queue, and the wave works the queue off at full
+ * width when it is full and once at its end: one entry per lane, one event
+ * reservation for all of them.  A queue takes C2D_EVQ_WORDS * C2D_EVQ_MAX
+ * doubles of LDS whatever its capacity; where they do not fit beside the
+ * tallies without costing a resident workgroup, the host leaves it off. */
+#define C2D_EVQ_WORDS 8
+#define C2D_EVQ_MAX 64
 /* generation-0 work items are split into C2D_WORK_SHARDS contiguous ranges,
  * each with its own fetch counter (one per 128-B line); a workgroup starts
  * on shard blockIdx % C2D_WORK_SHARDS and moves on when it is exhausted */
@@ -326,6 +335,8 @@ struct KParams {
   unsigned long long* cnt;  /* [C2D_NCOUNTERS] */
   int32_t* err;
   int32_t lds_cells;        /* 1: cell tallies privatised in LDS */
+  int32_t evq_cap;          /* bundle kernel: entries of each wave's escape queue in LDS, after
+                               the escape tallies (1..C2D_EVQ_MAX); 0: escapes handled inline */
   unsigned long long* prof;  /* [C2D_TR_PROF_WORDS] section counters (-DC2D_TR_PROF builds) */
   /* guide rows of the emission CDFs (eps_linear == 0): cdf_guide[(t * ncell + cell) *
    * (C2D_CDF_GUIDE + 1) + q] = the smallest i in [1, 400] with cdf(i) >= q / C2D_CDF_GUIDE

@@ -39,11 +39,11 @@ extern "C" int c2d_transport_occupancy_fast(int* blocks_per_cu, size_t lds, int 
 extern "C" int c2d_aux_occupancy_exact(int which, int* blocks_per_cu);
 extern "C" int c2d_aux_occupancy_fast(int which, int* blocks_per_cu);
 extern "C" int c2d_launch_bundle_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
-                                       int trk, hipStream_t s);
+                                       int trk, int evq, hipStream_t s);
 extern "C" int c2d_launch_bundle_fast(const KParams* P, const GenArgs* A, int grid, size_t lds,
-                                      int trk, hipStream_t s);
-extern "C" int c2d_bundle_occupancy_exact(int* blocks_per_cu, size_t lds, int trk);
-extern "C" int c2d_bundle_occupancy_fast(int* blocks_per_cu, size_t lds, int trk);
+                                      int trk, int evq, hipStream_t s);
+extern "C" int c2d_bundle_occupancy_exact(int* blocks_per_cu, size_t lds, int trk, int evq);
+extern "C" int c2d_bundle_occupancy_fast(int* blocks_per_cu, size_t lds, int trk, int evq);
 extern "C" int c2d_launch_comtab_sigma(const double* gnt, double* S, hipStream_t s);
 extern "C" int c2d_launch_comtab_gemm(const double* f_nt, const double* gnt, const double* S,
                                       double* tab, int ncell, hipStream_t s);
@@ -142,6 +142,7 @@ struct c2d_ctx {
   int bundle = 1, bundle_grid = 0;
   int src_grid = 0, sc_grid = 0;   /* CUs x resident blocks of the source / scatter kernels */
   size_t bundle_lds = 0;
+  int evq_cap = 0;                 /* entries of a wave's escape queue in LDS (KParams.evq_cap) */
   /* census SoA(s) of cens_phys records each.  Double-buffered:
    * census_capacity + one append chunk per wave slot; the compaction's work
    * lists (cscan_cap slots each).  Chunked (census_inplace, c2d_device.hpp
@@ -455,10 +456,31 @@ extern "C" int c2d_init(const c2d_config* cfg, c2d_ctx** out) {
     auto occ = cfg->comtot_mode == C2D_COMTOT_TABLE ? c2d_bundle_occupancy_fast
                                                     : c2d_bundle_occupancy_exact;
     int b0 = 0;
-    orc = occ(&b0, c->lds_bytes, cfg->trk_variant);
+    orc = occ(&b0, c->lds_bytes, cfg->trk_variant, 0);
     if (orc) return fail(c, C2D_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)orc));
     c->bundle_lds = c->lds_bytes;
     c->bundle_grid = c->n_cu * std::max(1, b0);
+    /* the waves' escape queues (C2D_EVQ_MAX entries each, whatever the
+     * capacity) take LDS the tallies leave free, if that keeps the kernel's
+     * resident workgroups per CU; else the inline path (large grids).  Test
+     * knob C2D_EVQ: 0 forces the inline path, n a capacity of n (if a
+     * workgroup with the queues fits at all). */
+    const size_t evq_lds = sizeof(double) * C2D_EVQ_WORDS * C2D_EVQ_MAX * (C2D_TR_BLOCK / 64);
+    int cap = C2D_EVQ_MAX, need = b0;
+    if (const char* e = getenv("C2D_EVQ")) {
+      cap = (int)std::max<long long>(0, std::min<long long>(C2D_EVQ_MAX, atoll(e)));
+      need = 1;
+    }
+    if (cap > 0 && b0 > 0) {
+      int b1 = 0;
+      orc = occ(&b1, c->lds_bytes + evq_lds, cfg->trk_variant, 1);
+      if (orc) return fail(c, C2D_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)orc));
+      if (b1 >= need) {
+        c->evq_cap = cap;
+        c->bundle_lds = c->lds_bytes + evq_lds;
+        c->bundle_grid = c->n_cu * b1;
+      }
+    }
   }
   {
     auto aocc = cfg->comtot_mode == C2D_COMTOT_TABLE ? c2d_aux_occupancy_fast : c2d_aux_occupancy_exact;
@@ -1411,6 +1433,7 @@ static int run_step_body(c2d_ctx* c) {
   P.cnt = c->ctl + CTL_CNT;
   P.err = c->derr;
   P.lds_cells = c->lds_cells;
+  P.evq_cap = c->evq_cap;
   P.prof = c->ctl + CTL_PROF;
   P.n_vol_global = c->n_vol_global;
   P.n_surf_global = c->n_surf_global;
@@ -1514,7 +1537,7 @@ static int run_step_body(c2d_ctx* c) {
       const int grid = (int)std::max<int64_t>(
           1, std::min<int64_t>(gmax, (A.n_items + C2D_TR_BLOCK - 1) / C2D_TR_BLOCK));
       c->g0_launched = true;
-      int rc = launch_b(c->dP, &A, grid, c->bundle_lds, cfg.trk_variant, c->stream);
+      int rc = launch_b(c->dP, &A, grid, c->bundle_lds, cfg.trk_variant, c->evq_cap > 0, c->stream);
       if (rc) return fail(c, C2D_E_HIP, "bundle launch (gen 0): %s", hipGetErrorString((hipError_t)rc));
       launches++;
     }

@@ -947,6 +947,90 @@ C2D_COLD_FN int imcleak(const KParams& P0, const Tal& T, Pkt& p, LaneCnt& lc) {
   return 1;
 }
 
+/* The bundle kernel's per-wave escape queue (KParams.evq_cap > 0,
+ * c2d_device.hpp): imcleak's work but the axis pass-through, taken out of the
+ * lane loop.  A wave's queue is C2D_EVQ_WORDS columns of C2D_EVQ_MAX doubles in
+ * the dynamic LDS after the escape tallies, whatever its capacity (a constant
+ * stride: the column offsets are immediates of the ds instructions; a
+ * run-time stride cost the kernel 2 VGPRs it does not have).  Lane i of a
+ * push or a flush touches element i of each column: no bank conflicts.
+ *   xnu, ew, rpre, zpre, wmu, azimuth, dcen, tag
+ * azimuth: Etan, the cosine the flight carries (fast build: no acos in the
+ * loop), or phi (exact build); tag: kph | jph << 16 | quadrant switch << 31
+ * in the low word, the packet's bins in the high one. */
+/* offset of the wave's queue in c2d_tr_lds (wave-uniform: kept in an SGPR) */
+__device__ __forceinline__ int evq_offset(int evq_off) {
+  return evq_off + __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) * C2D_EVQ_WORDS * C2D_EVQ_MAX));
+}
+__device__ __forceinline__ void evq_store(double* q, uint32_t i, const Pkt& p) {
+  constexpr uint32_t cap = C2D_EVQ_MAX;
+  q[i] = p.xnu;
+  q[cap + i] = p.ew;
+  q[2 * cap + i] = p.rpre;
+  q[3 * cap + i] = p.zpre;
+  q[4 * cap + i] = p.wmu;
+#if C2D_TABLE_COMTOT
+  q[5 * cap + i] = p.eta;
+  const uint32_t sw = p.esw == -1 ? 0x80000000u : 0u;
+#else
+  q[5 * cap + i] = p.phi;
+  const uint32_t sw = 0u;
+#endif
+  q[6 * cap + i] = p.dcen;
+  const uint64_t tag = ((uint64_t)p.bins << 32) | (uint64_t)((uint32_t)p.kph | ((uint32_t)p.jph << 16) | sw);
+  q[7 * cap + i] = __longlong_as_double((long long)tag);
+}
+
+/* Lanes 0..n-1 take entry `lane` each: imcleak for a copy that leaves
+ * (imcleak2d.f:2-320), the same arithmetic as the inline path, and one event
+ * reservation for all the lanes that write one.  Every lane of the wave calls
+ * it. */
+__device__ __forceinline__ void evq_flush(const KParams& P0, const Tal& T, const double* q,
+                                          uint32_t n, uint32_t lane, LaneCnt& lc) {
+  constexpr uint32_t cap = C2D_EVQ_MAX;
+  const KParams& P = cold(P0);
+  if (lane >= n) return;
+  Pkt p;
+  p.xnu = q[lane];
+  p.ew = q[cap + lane];
+  p.rpre = q[2 * cap + lane];
+  p.zpre = q[3 * cap + lane];
+  p.wmu = q[4 * cap + lane];
+  const double az = q[5 * cap + lane];
+  p.dcen = q[6 * cap + lane];
+  const uint64_t tag = (uint64_t)__double_as_longlong(q[7 * cap + lane]);
+  p.bins = (uint32_t)(tag >> 32);
+  p.kph = (int32_t)(tag & 0xffffu);
+  p.jph = (int32_t)((tag >> 16) & 0x7fffu);
+  LC_ADD(lc, C2D_CNT_ESCAPES);
+  if (p.kph == 0) {                      /* inner surface, rmin > 1e-10 (the axis is not queued) */
+    atomicAdd(&T_ERLKI(P, T)[p.jph - 1], p.ew);
+    return;
+  }
+  bool ev = P.ncycle > 0;
+  if (p.jph <= 0) {
+    if (P.tbbl[p.kph - 1] > 0.0) {
+      gadd(&P.T[P.off.Ed_in + p.kph - 1], p.ew);
+      atomicAdd(&T_ERLKL(P, T)[p.kph - 1], p.ew);
+    }
+  } else if (p.jph != P.nz + 1) {
+    atomicAdd(&T_ERLKO(P, T)[p.jph - 1], p.ew);
+  } else {
+    atomicAdd(&T_ERLKU(P, T)[p.kph - 1], p.ew);
+    ev = ev && p.wmu < F32(0.98);
+  }
+  if (!ev) return;
+#if C2D_TABLE_COMTOT
+  p.phi = c2d_acos(az);
+  if (tag & 0x80000000ull) p.phi = 2.0 * PI_REF - p.phi;
+#else
+  p.phi = az;
+#endif
+  const double tb = P.time + P.dt - RAD_CP * p.dcen;   /* H4: fresh t_bound everywhere */
+  push_event(P, tb, p, lc);
+  escape_tally(P, T, p);
+}
+
 /* Census appends come from wave-private chunks of P.cens_chunk slots,
  * reserved with one atomic (a single address every wave appends to:
  * per-write reservations were the kernel's limiter).
@@ -1253,8 +1337,14 @@ enum : int {
   TP_LEAK_W = 14, TP_LEAK_L = 15,     /* imcleak calls                  */
   TP_COLL_W = 16, TP_COLL_L = 17,     /* collisions                     */
   TP_RST_W = 18, TP_RST_L = 19,       /* probe restarts                 */
-  TP_NWAVE = 20
+  TP_NWAVE = 20,
+  TP_FLUSH = 21,    /* bundle: escape-queue flushes (evq_flush), cycles     */
+  TP_FLUSH_W = 22, TP_FLUSH_L = 23    /* ... flushes, entries           */
 };
+/* the branch counts TP_GOT_W .. TP_RST_L: one per execution by a wave, whichever
+ * of its lanes are in the branch (the first of them counts; the lanes' counts
+ * are summed at the end), so count / TP_ITER is the share of iterations */
+enum : int { TP_CNT0 = TP_GOT_W, TP_CNT1 = TP_RST_L };
 struct Prof {
 #ifdef C2D_TR_PROF
   uint64_t acc[C2D_TR_PROF_WORDS];
@@ -1263,7 +1353,19 @@ struct Prof {
 };
 #ifdef C2D_TR_PROF
 #define TP_MARK(pf, i) do { const uint64_t _n = clock64(); (pf).acc[i] += _n - (pf).t; (pf).t = _n; } while (0)
-#define TP_COUNT(pf, iw, il) do { (pf).acc[iw] += 1; (pf).acc[il] += __popcll(__ballot(1)); } while (0)
+#define TP_COUNT(pf, iw, il) do {                                                         \
+    const unsigned long long _m = __ballot(1);                                            \
+    if (lane_id() == (uint32_t)(__ffsll((long long)_m) - 1)) {                            \
+      (pf).acc[iw] += 1; (pf).acc[il] += __popcll(_m);                                    \
+    }                                                                                     \
+  } while (0)
+/* timers and iteration counts from lane 0, the branch counts from every lane */
+#define TP_REPORT(pf, P, lane) do {                                                       \
+    (pf).acc[TP_NWAVE] = 1;                                                               \
+    for (int i = 0; i < C2D_TR_PROF_WORDS; i++)                                           \
+      if ((pf).acc[i] && ((lane) == 0 || (i >= TP_CNT0 && i <= TP_CNT1)))                 \
+        atomicAdd(&(P).prof[i], (unsigned long long)(pf).acc[i]);                         \
+  } while (0)
 #else
 #define TP_MARK(pf, i) do { } while (0)
 #define TP_COUNT(pf, iw, il) do { } while (0)
@@ -2276,10 +2378,7 @@ __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_transport_kerne
     TP_MARK(pf, TP_POST);
   }
 #ifdef C2D_TR_PROF
-  pf.acc[TP_NWAVE] = 1;
-  if (lane == 0)
-    for (int i = 0; i < C2D_TR_PROF_WORDS; i++)
-      if (pf.acc[i]) atomicAdd(&P.prof[i], (unsigned long long)pf.acc[i]);
+  TP_REPORT(pf, P, lane);
 #endif
   census_chunk_store(P, tid >> 6, lane);
 
@@ -2350,7 +2449,8 @@ enum : int32_t {
   BF_SPEC = 2,      /* ... with a weight that assumes no more collisions */
   BF_RERUN = 4,     /* a collision cancelled it: refly alone afterwards  */
   BF_TKILL = 8,     /* it ended KILLED / ABORTED: counted at the bundle end */
-  BF_TABORT = 16
+  BF_TABORT = 16,
+  BF_ESCQ = 32      /* it left the grid in this step: p goes to the wave's escape queue */
 };
 struct Bundle {
   Pkt p;              /* shared path; p.ew, p.wtmin, p.ctr: the recombined copy's */
@@ -2470,7 +2570,7 @@ __device__ __forceinline__ void probe_collide(const KParams& P, const Tal& T, co
 }
 
 /* one shared step of the bundle (flight() for every copy on the path) */
-template <int V12>
+template <int V12, int EVQ>
 __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, const GenArgs& A,
                                             Bundle& b, ComCache& cc, LaneCnt& lc, Prof& pf,
                                             CensRec& nr, long long nitem, int& nst) {
@@ -2647,7 +2747,8 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
     const bool leaves = bnd && (jnew == P.nz + 1 || jnew == 0 || knew == P.nr + 1 || knew == 0);
 #if C2D_TABLE_COMTOT
     p.eta = Etan;
-    if ((b.flags & BF_TRACK) && leaves) {   /* an escape event reads phi (census: encoded) */
+    /* an escape event reads phi (census: encoded); queued escapes take the acos at the flush */
+    if (!EVQ && (b.flags & BF_TRACK) && leaves) {
       p.phi = c2d_acos(Etan);
       if (eta_switch == -1) p.phi = 2.0 * PI_REF - p.phi;
     }
@@ -2665,8 +2766,15 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
         p.kph = knew;
         if (b.flags & BF_TRACK) {
           TP_COUNT(pf, TP_LEAK_W, TP_LEAK_L);
-          if (imcleak(P, T, p, lc) == 1) b.flags &= ~BF_TRACK;
-          else set_phi(p, p.phi);               /* axis pass-through set phi = 1e-6 */
+          if (!EVQ) {
+            if (imcleak(P, T, p, lc) == 1) b.flags &= ~BF_TRACK;
+            else set_phi(p, p.phi);             /* axis pass-through set phi = 1e-6 */
+          } else if (p.kph == 0 && !(P.rmin > 1.0e-10)) {
+            p.kph = 1;                          /* imcleak's axis pass-through */
+            set_phi(p, 1.0e-6);
+          } else {
+            b.flags = (b.flags & ~BF_TRACK) | BF_ESCQ;   /* the rest of imcleak: evq_flush */
+          }
         }
       } else {
         p.kph = knew;
@@ -2819,7 +2927,9 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
   TP_MARK(pf, TP_PTS);
 }
 
-template <int V12>
+/* EVQ 1: escapes through the waves' queues (KParams.evq_cap >= 1), 0: inline
+ * (both paths in one kernel cost 2 VGPRs over the 168 of 3 waves per SIMD) */
+template <int V12, int EVQ>
 __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(const KParams* __restrict__ Pg,
                                                                    const GenArgs A) {
   const KParams& P = *Pg;
@@ -2865,6 +2975,10 @@ __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(
   CensRec nr = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0u, 0u, 0ull};
   long long nitem = 0;
   int nst = 0;
+  /* the wave's escape queue (evq_flush): its capacity (0: inline escapes) and fill */
+  const uint32_t evq_cap = EVQ ? (uint32_t)min(max(P.evq_cap, 1), C2D_EVQ_MAX) : 0u;
+  const int evq_off = evq_offset(T.esc_off + n_esc);
+  uint32_t evq_n = 0;              /* wave-uniform */
 
   /* chunked, wave-aggregated work fetch from the workgroup's shard of the
    * item range, then from the following ones: every lane with `want` gets
@@ -2958,14 +3072,53 @@ __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(
       bundle_begin(P, T, b, from_pf, &nr);
       busy = true;
     }
-    if (exhausted && __ballot(busy) == 0ull) break;
+    const bool done = exhausted && __ballot(busy) == 0ull;
+    if (done && evq_n == 0) break;
     TP_MARK(pf, TP_START);
     if (busy) {
 #ifdef C2D_TR_PROF
       pf.acc[TP_LANES] += __popcll(__ballot(1));
 #endif
-      bundle_step<V12>(P, T, A, b, cc, lc, pf, nr, nitem, nst);
+      bundle_step<V12, EVQ>(P, T, A, b, cc, lc, pf, nr, nitem, nst);
       TP_MARK(pf, TP_EVENT);
+    }
+    if (EVQ) {
+      /* the copies that left in this step go to the wave's queue, by rank
+       * among them; the ones that do not fit wait for the flush.  After the
+       * last step (done: no lane has work or will get any) the queue drains. */
+      unsigned long long em = __ballot(busy && (b.flags & BF_ESCQ));
+      while (em != 0ull || done) {
+        const uint32_t room = evq_cap - evq_n;
+        const uint32_t ne = (uint32_t)__popcll(em);
+        const unsigned long long lt = (lane == 0) ? 0ull : (em & ((~0ull) >> (64 - lane)));
+        const uint32_t rank = (uint32_t)__popcll(lt);
+        if (((em >> lane) & 1ull) && rank < room) {
+          evq_store(c2d_tr_lds + evq_off, evq_n + rank, b.p);
+          b.flags &= ~BF_ESCQ;
+        }
+        if (ne <= room && !done) {
+          evq_n = __builtin_amdgcn_readfirstlane(evq_n + ne);
+          break;
+        }
+        evq_n = __builtin_amdgcn_readfirstlane(evq_n + (ne < room ? ne : room));
+        /* LDS accesses of one wave complete in order: the fence only keeps
+         * the compiler from moving the reads above the stores */
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        TP_MARK(pf, TP_EVENT);
+#ifdef C2D_TR_PROF
+        if (lane == 0) { pf.acc[TP_FLUSH_W] += 1; pf.acc[TP_FLUSH_L] += evq_n; }
+#endif
+        evq_flush(P, T, c2d_tr_lds + evq_off, evq_n, lane, lc);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        TP_MARK(pf, TP_FLUSH);
+        evq_n = 0;
+        if (done) break;
+        em = __ballot(busy && (b.flags & BF_ESCQ));
+      }
+    }
+    if (done) break;
+    if (busy) {
       if (!b.alive && !(b.flags & BF_TRACK)) {
         if ((b.flags & (BF_TKILL | BF_RERUN)) == BF_TKILL)
           LC_ADD(lc, (b.flags & BF_TABORT) ? C2D_CNT_ABORTED : C2D_CNT_KILLED);
@@ -2987,10 +3140,7 @@ __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(
     TP_MARK(pf, TP_POST);
   }
 #ifdef C2D_TR_PROF
-  pf.acc[TP_NWAVE] = 1;
-  if (lane == 0)
-    for (int i = 0; i < C2D_TR_PROF_WORDS; i++)
-      if (pf.acc[i]) atomicAdd(&P.prof[i], (unsigned long long)pf.acc[i]);
+  TP_REPORT(pf, P, lane);
 #endif
 
   census_chunk_store(P, tid >> 6, lane);
@@ -3088,35 +3238,35 @@ extern "C" int C2D_SFX(c2d_launch_transport)(const c2d::KParams* P_dev, const c2
   return (int)hipGetLastError();
 }
 
+static const void* C2D_SFX(bundle_fn)(int trk, int evq) {
+  if (trk) return evq ? (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<1, 1> : (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<1, 0>;
+  return evq ? (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<0, 1> : (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<0, 0>;
+}
+
 static int C2D_SFX(bundle_lds_attr)(size_t lds_bytes) {
   if (lds_bytes <= 64 * 1024) return 0;
-  for (const void* k : {(const void*)C2D_SFX(c2d::c2d_bundle_kernel)<0>,
-                        (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<1>})
-    if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes))
+  for (int v = 0; v < 4; v++)
+    if (hipError_t e = hipFuncSetAttribute(C2D_SFX(bundle_fn)(v >> 1, v & 1),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes))
       return (int)e;
   return 0;
 }
 
+/* evq: KParams.evq_cap > 0 (the escape-queue instance; lds_bytes includes the queues) */
 extern "C" int C2D_SFX(c2d_launch_bundle)(const c2d::KParams* P_dev, const c2d::GenArgs* A, int grid,
-                                          size_t lds_bytes, int trk, hipStream_t stream) {
+                                          size_t lds_bytes, int trk, int evq, hipStream_t stream) {
   if (int e = C2D_SFX(bundle_lds_attr)(lds_bytes)) return e;
-  if (trk)
-    hipLaunchKernelGGL(C2D_SFX(c2d::c2d_bundle_kernel)<1>, dim3(grid), dim3(c2d::BLOCK), lds_bytes,
-                       stream, P_dev, *A);
-  else
-    hipLaunchKernelGGL(C2D_SFX(c2d::c2d_bundle_kernel)<0>, dim3(grid), dim3(c2d::BLOCK), lds_bytes,
-                       stream, P_dev, *A);
-  return (int)hipGetLastError();
+  void* args[] = {(void*)&P_dev, (void*)A};
+  return (int)hipLaunchKernel(C2D_SFX(bundle_fn)(trk, evq), dim3(grid), dim3(c2d::BLOCK), args, lds_bytes,
+                              stream);
 }
 
 /* trk: the tracker instance the context launches (c2d_config.trk_variant):
- * its own VGPR count sets the resident blocks */
-extern "C" int C2D_SFX(c2d_bundle_occupancy)(int* blocks_per_cu, size_t lds_bytes, int trk) {
+ * the occupancy is that instance's */
+extern "C" int C2D_SFX(c2d_bundle_occupancy)(int* blocks_per_cu, size_t lds_bytes, int trk, int evq) {
   if (C2D_SFX(bundle_lds_attr)(lds_bytes) != 0) { *blocks_per_cu = 0; return 0; }
-  return (int)(trk ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                         blocks_per_cu, C2D_SFX(c2d::c2d_bundle_kernel)<1>, c2d::BLOCK, lds_bytes)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                         blocks_per_cu, C2D_SFX(c2d::c2d_bundle_kernel)<0>, c2d::BLOCK, lds_bytes));
+  return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, C2D_SFX(bundle_fn)(trk, evq),
+                                                           c2d::BLOCK, lds_bytes);
 }
 
 extern "C" int C2D_SFX(c2d_launch_source)(const c2d::KParams* P_dev, int grid, hipStream_t stream) {
