@@ -234,6 +234,11 @@ __device__ __forceinline__ void gadd(double* p, double v) {
   __hip_atomic_fetch_add((C2D_GLOBAL double*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+/* atomicAdd's relaxed, agent-scope fetch-add on a KParams pointer (returns the old value) */
+__device__ __forceinline__ unsigned long long gadd_u64(unsigned long long* p, unsigned long long v) {
+  return __hip_atomic_fetch_add((C2D_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ void gor(int32_t* p, int32_t v) {
   __hip_atomic_fetch_or((C2D_GLOBAL int32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -921,7 +921,7 @@ C2D_COLD_FN int imcleak(const KParams& P0, const Tal& T, Pkt& p, LaneCnt& lc) {
   LC_ADD(lc, C2D_CNT_ESCAPES);
   const double tb = P.time + P.dt - RAD_CP * p.dcen;   /* H4: fresh t_bound everywhere */
   if (p.jph <= 0) {
-    if (P.tbbl[p.kph - 1] > 0.0) {
+    if (gld(P.tbbl + (p.kph - 1)) > 0.0) {
       gadd(&P.T[P.off.Ed_in + p.kph - 1], p.ew);
       atomicAdd(&T_ERLKL(P, T)[p.kph - 1], p.ew);
     }
@@ -1009,7 +1009,7 @@ __device__ __forceinline__ void evq_flush(const KParams& P0, const Tal& T, const
   }
   bool ev = P.ncycle > 0;
   if (p.jph <= 0) {
-    if (P.tbbl[p.kph - 1] > 0.0) {
+    if (gld(P.tbbl + (p.kph - 1)) > 0.0) {
       gadd(&P.T[P.off.Ed_in + p.kph - 1], p.ew);
       atomicAdd(&T_ERLKL(P, T)[p.kph - 1], p.ew);
     }
@@ -1073,17 +1073,17 @@ C2D_COLD_FN unsigned long long census_new_chunk(const KParams& P0, int w) {
                           __HIP_MEMORY_SCOPE_AGENT) > __hip_atomic_load((C2D_GLOBAL unsigned long long*)
                                                                           P.relist_head, __ATOMIC_RELAXED,
                                                                         __HIP_MEMORY_SCOPE_AGENT)) {
-      const unsigned long long h = atomicAdd(P.relist_head, 1ull);
+      const unsigned long long h = gadd_u64(P.relist_head, 1ull);
       if (h < gld(P.n_relist))
         id = __hip_atomic_load((C2D_GLOBAL int32_t*)(P.relist + h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (id < 0) {
-      const unsigned long long h = atomicAdd(P.pool_head, 1ull);
+      const unsigned long long h = gadd_u64(P.pool_head, 1ull);
       if (h < gld(P.pool_n)) id = gld(P.pool + h);
     }
   }
   if (id < 0) return (unsigned long long)P.cap_cout;
-  gst(P.out_list + atomicAdd(P.n_out, 1ull), id);
+  gst(P.out_list + gadd_u64(P.n_out, 1ull), id);
   return (unsigned long long)id << C2D_CCHUNK_LOG;
 }
 
@@ -1132,7 +1132,7 @@ __device__ __forceinline__ void census_chunk_load(const KParams& P0, int w, uint
 
 /* a freed chunk the wave cannot keep goes to the relist */
 __device__ __forceinline__ void census_relist(const KParams& P, int32_t id) {
-  const unsigned long long h = atomicAdd(P.n_relist, 1ull);
+  const unsigned long long h = gadd_u64(P.n_relist, 1ull);
   __hip_atomic_store((C2D_GLOBAL int32_t*)(P.relist + h), id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -1426,7 +1426,7 @@ __device__ __forceinline__ int flight(const KParams& P, const Tal& T, Pkt& p, Co
 #endif
   }
   const double sigsc = comac;
-  const double rkm1 = (p.kph == 1) ? P.rmin : g->r[p.kph - 1];
+  const double rkm1 = g->r[p.kph - 1];                 /* r[0] = rmin */
   const double xqsqleft = rkm1 * rkm1;
   double dcol;
   if (p.mode != 0)
@@ -1450,14 +1450,12 @@ __device__ __forceinline__ int flight(const KParams& P, const Tal& T, Pkt& p, Co
   const double rpre = p.rpre, zpre = p.zpre, wmu = p.wmu;
   const double disp = Eta * rpre;
   const double psq = rpre * rpre * (1.0 - Eta * Eta);
-  int kbnd, inout, knew, jnew;
+  int inout, knew, jnew;
   double rbnd, Zbnd;
   if (Eta < 0.0 && psq < xqsqleft) {
-    kbnd = p.kph - 1;
     inout = -1;
     rbnd = rkm1;
   } else {
-    kbnd = p.kph;
     inout = 1;
     rbnd = g->r[p.kph];
   }
@@ -1468,7 +1466,7 @@ __device__ __forceinline__ int flight(const KParams& P, const Tal& T, Pkt& p, Co
   double trldb = disbr / swmu;
   double fr = disbr;                           /* the reference's f (imctrk2d.f:278,290,380) */
   const double Zr = zpre + wmu * trldb;
-  const double zlow = (p.jph == 1) ? P.zmin : g->z[p.jph - 1];
+  const double zlow = g->z[p.jph - 1];                 /* z[0] = zmin */
   const double zup = g->z[p.jph];
   if (Zr > zup || Zr < zlow) {
     Zbnd = (Zr > zup) ? zup : zlow;
@@ -1481,7 +1479,7 @@ __device__ __forceinline__ int flight(const KParams& P, const Tal& T, Pkt& p, Co
   } else {
     knew = p.kph + inout;
     jnew = p.jph;
-    rbnd = (kbnd > 0) ? g->r[kbnd] : P.rmin;
+    /* rbnd stays the grid radius read above (r[0] = rmin) */
     Zbnd = Zr;
   }
   double rnew, znew;
@@ -2187,6 +2185,10 @@ __global__ void __launch_bounds__(SBLOCK) C2D_SFX(c2d_scatter_hard_kernel)(const
  * packet-store entry -src - 1 */
 /* a census record's columns as loaded (the census branch of load_source):
  * issued by pf_issue, turned into the packet by pf_apply */
+/* s_waitcnt immediate of gfx9: vmcnt(0) alone (expcnt 7 and lgkmcnt 15, their
+ * maxima, wait for nothing) */
+constexpr int C2D_WAIT_VMCNT0 = 0x0F70;
+
 struct CensRec {
   double rpre, zpre, wmu, cphi, ew, xnu;
   uint32_t jk, bn;
@@ -2251,7 +2253,7 @@ __device__ __forceinline__ void pf_issue_lds(const KParams& P0, long long i) {
 }
 __device__ __forceinline__ void pf_read_lds(CensRec& r) {
   /* the loads' LDS writes complete in vmcnt order: wait for all of them */
-  __builtin_amdgcn_s_waitcnt(0xF70);                 /* vmcnt(0) */
+  __builtin_amdgcn_s_waitcnt(C2D_WAIT_VMCNT0);
   const int w = (int)(threadIdx.x >> 6), l = (int)(threadIdx.x & 63);
   auto dbl = [&](int f) {
     return __hiloint2double((int)c2d_pf_lds[w][2 * f + 1][l], (int)c2d_pf_lds[w][2 * f][l]);
@@ -2595,7 +2597,13 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
   lc.paths++;
   const int cell = (p.jph - 1) * P.nr + (p.kph - 1);
   /* the step's absorption coefficient: issued before the comtot lookup and
-   * the geometry, used after them */
+   * the geometry, used after them (vmcnt is one in-order counter: with live
+   * probes the wait for the table points, issued after it, covers it; the
+   * geometry's grid reads are LDS reads and wait for lgkmcnt only) */
+  /* (the table's pointer itself comes by a vector load the wave waits for
+   * first: the select below is compiled as a select of the fields' addresses.
+   * Selecting the scalar-loaded pointers by value removed that wait and
+   * gained nothing, profiles/r13a) */
   const double kap_cell = gld((KAP(p) ? P.kappa_s : P.kappa_cv) + (int64_t)cell * C2D_N_VOL + ((p.ie & 0xffff) - 1));
   double sigsc = 1.0;
   if (b.alive) {
@@ -2615,7 +2623,7 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
 #endif
   }
   /* geometry (imctrk2d.f:228-379), shared */
-  const double rkm1 = (p.kph == 1) ? P.rmin : g->r[p.kph - 1];
+  const double rkm1 = g->r[p.kph - 1];                 /* r[0] = rmin */
   const double xqsqleft = rkm1 * rkm1;
 #if C2D_TABLE_COMTOT
   double Eta = p.eta;
@@ -2628,14 +2636,12 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
   const double rpre = p.rpre, zpre = p.zpre, wmu = p.wmu;
   const double disp = Eta * rpre;
   const double psq = rpre * rpre * (1.0 - Eta * Eta);
-  int kbnd, inout, knew, jnew;
+  int inout, knew, jnew;
   double rbnd, Zbnd;
   if (Eta < 0.0 && psq < xqsqleft) {
-    kbnd = p.kph - 1;
     inout = -1;
     rbnd = rkm1;
   } else {
-    kbnd = p.kph;
     inout = 1;
     rbnd = g->r[p.kph];
   }
@@ -2646,7 +2652,7 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
   double trldb = FDIV_POS(disbr, swmu);
   double fr = disbr;                    /* V12: the reference's f on a boundary step */
   const double Zr = zpre + wmu * trldb;
-  const double zlow = (p.jph == 1) ? P.zmin : g->z[p.jph - 1];
+  const double zlow = g->z[p.jph - 1];                 /* z[0] = zmin */
   const double zup = g->z[p.jph];
   if (Zr > zup || Zr < zlow) {
     Zbnd = (Zr > zup) ? zup : zlow;
@@ -2659,7 +2665,7 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
   } else {
     knew = p.kph + inout;
     jnew = p.jph;
-    rbnd = (kbnd > 0) ? g->r[kbnd] : P.rmin;
+    /* rbnd stays the grid radius read above (r[0] = rmin) */
     Zbnd = Zr;
   }
   /* every copy that does not collide: boundary if trldb < dcen, else census */
@@ -2713,6 +2719,17 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
     }
   }
   TP_MARK(pf, TP_ABS);
+  /* Every load this step issued has been consumed by now: kap_cell by xabs
+   * (before TP_GEOM), the comtot table points by sigsc in the collision loop
+   * above, under the same b.alive that issued them.  So the wave's vmcnt is
+   * already 0 here unless a probe collided in this step (push_scat's stores),
+   * and this wait costs nothing.  What it resets is the compiler's waitcnt
+   * scoreboard: that is path-insensitive across exec-mask branches and kept
+   * the table loads pending on the (impossible) path that issues them and
+   * skips their use, which turned the next definitions of their registers,
+   * before pf_issue and before the point loop below, into vmcnt(0) drains of
+   * the census stores and of the prefetch itself (profiles/r13a). */
+  __builtin_amdgcn_s_waitcnt(C2D_WAIT_VMCNT0);
   /* ---- the recombined copy (mode 0) ---- */
   if (b.flags & BF_TRACK) {
     lc.steps++;
@@ -2726,7 +2743,10 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
    * and escape events are stored here, before the survivors' point loop:
    * stores and the n_field atomic count in vmcnt with the loads, so the
    * VALU-only loop below lets them drain before the next load is waited
-   * for. ---- */
+   * for.  (As compiled this held only since the scoreboard reset above:
+   * until then a vmcnt(0) before pf_issue drained them, and a second one
+   * before the point loop drained the prefetch; tools/lane_loop_waits.py,
+   * tests/test_lane_loop_waits.py.) ---- */
   if (b.alive || (b.flags & BF_TRACK)) {
     double rnew, znew;
     if (bnd) {
@@ -2760,7 +2780,10 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
     p.zpre = znew;
     TP_MARK(pf, TP_EVENT);
     if (bnd) {
-      if (leaves) {
+      /* unlikely per lane: keeps the inline imcleak (EVQ 0), with its returning
+       * atomics and their waits, out of the block layout between the census
+       * write and the point loop; the queue instances compile unchanged */
+      if (__builtin_expect(leaves, 0)) {
         b.alive = 0;                            /* probes leaving end (no tally) */
         p.jph = jnew;
         p.kph = knew;
@@ -2797,7 +2820,9 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
 #if C2D_PF_SRC
   /* the step's own loads have been waited for and its records stored: the
    * next source's record loads issue here and complete under the VALU-only
-   * point loop and the refill */
+   * point loop and the refill (the first vmcnt wait after them is pf_apply's
+   * in the next iteration; cold paths between, a queue flush or a new work
+   * chunk, wait earlier) */
   if (nst == 1 && nitem >= 0) {
 #if C2D_PF_LDS
     pf_issue_lds(P, nitem);
