@@ -340,6 +340,8 @@ class StepInputs:
 # ---------------------------------------------------------------------------
 C2D_E_FP = -8
 C2D_E_NONFINITE = -11
+C2D_E_STATE = -7
+C2D_E_IO = -10          # c2d_events_write*, c2d_events_read, c2d_obs*_accumulate_file
 ERRORS[C2D_E_FP] = "C2D_E_FP"
 FP_E_OLD, FP_E_NEW, FP_HR, FP_HR_ST, FP_DELTA_T, FP_STEPS, FP_SKIPPED = range(7)
 FP_NDIAG = 8

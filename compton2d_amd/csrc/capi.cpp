@@ -22,6 +22,7 @@
 #include "c2d_rng.h"
 #include "pspt_host.h"
 #include "plcm_host.h"
+#include "c2d_evparse.hpp"
 #include "c2d_evtext.hpp"
 
 using namespace c2d;
@@ -198,6 +199,8 @@ struct c2d_ctx {
   bool ev_stepped = false;              /* a step has filled (or emptied) the event buffer */
   c2d_evt_writer* evt = nullptr;        /* c2d_events_write's staging buffers (evtext.hip) */
   c2d_evt_times evt_times = {};         /* of the last c2d_events_write* */
+  c2d_evt_reader* evr = nullptr;        /* c2d_events_read's staging buffers (evparse.hip) */
+  c2d_evr_times evr_times = {};         /* of the last c2d_events_read / c2d_obs*_accumulate_file */
   /* the context's own escapes binned on a second stream (c2d_obs_accumulate
    * with no events): it overlaps the next step's FP / tables / sources, and
    * the next generation-0 launch, which rewrites the event buffer, waits
@@ -550,6 +553,7 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
   if (c->obs_stream) (void)hipStreamSynchronize(c->obs_stream);   /* it reads the event buffer */
   if (c->mono_flag) (void)hipFree(c->mono_flag);
   c2d_evtext_free(c->evt);
+  c2d_evparse_free(c->evr);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   void* ptrs[] = {c->geo, c->gnt, c->kappa_cur, c->kappa_prev, c->eps_tot, c->eps_th, c->f_nt,
                   c->Pnt, c->n_e, c->vfrac, c->ewsv, c->surf_ew, c->surf_tbb, c->tbbl,
@@ -3316,5 +3320,96 @@ extern "C" int c2d_last_events_write_ms(c2d_ctx* c, double* scan_ms, double* ker
   if (ambiguous) *ambiguous = c->evt_times.ambiguous;
   if (multilimb) *multilimb = c->evt_times.multilimb;
   if (chunks) *chunks = c->evt_times.chunks;
+  return C2D_OK;
+}
+
+/* ------------------------------------------------------------------------
+ * p###_evb.dat text back to events, parsed on the device (evparse.hip)
+ * ---------------------------------------------------------------------- */
+static int events_parse(c2d_ctx* c, const char* path, c2d_evr_sink sink, void* user, int64_t* n) {
+  char err[768] = "";
+  int64_t got = 0;
+  const int rc = c2d_evparse_file(&c->evr, c->cfg.device, c->stream, path, sink, user, &got, &c->evr_times, err,
+                                  sizeof err);
+  if (n) *n = got;
+  /* a sink that failed has left its own message */
+  return rc ? (err[0] ? fail(c, rc, "%s", err) : rc) : C2D_OK;
+}
+
+namespace {
+struct EvReadDst {
+  c2d_ctx* c;
+  double* buf;
+  int64_t cap, done;
+  bool on_device;
+};
+}  // namespace
+
+static int events_read_sink(void* user, const double* ev, int64_t n, int on_device) {
+  EvReadDst* d = static_cast<EvReadDst*>(user);
+  const int64_t m = std::min(n, d->cap - d->done);
+  if (m <= 0) return C2D_OK;
+  if (!on_device && !d->on_device) {
+    memcpy(d->buf + d->done * C2D_EVENT_WORDS, ev, (size_t)m * C2D_EVENT_WORDS * sizeof(double));
+    d->done += m;
+    return C2D_OK;
+  }
+  const hipMemcpyKind kind = on_device ? (d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost)
+                                       : hipMemcpyHostToDevice;
+  /* on the context's stream, behind the parse kernel; waited for, because the
+   * staging buffer (or the host parser's vector) is reused on return */
+  HIPCHK(d->c, hipMemcpyAsync(d->buf + d->done * C2D_EVENT_WORDS, ev, (size_t)m * C2D_EVENT_WORDS * sizeof(double), kind,
+                              d->c->stream));
+  HIPCHK(d->c, hipStreamSynchronize(d->c->stream));
+  d->done += m;
+  return C2D_OK;
+}
+
+extern "C" int c2d_events_read(c2d_ctx* c, const char* path, double* buf, int64_t cap, int32_t on_device, int64_t* n) {
+  if (!c || !path || !path[0] || !n || cap < 0 || (cap > 0 && !buf)) return C2D_E_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  EvReadDst d = {c, buf, cap, 0, on_device != 0};
+  return events_parse(c, path, cap > 0 ? events_read_sink : nullptr, &d, n);
+}
+
+static int obs_file_sink(void* user, const double* ev, int64_t n, int on_device) {
+  c2d_ctx* c = static_cast<c2d_ctx*>(user);
+  return on_device ? obs_launch(c, ev, n) : c2d_obs_accumulate(c, ev, n);
+}
+
+extern "C" int c2d_obs_accumulate_file(c2d_ctx* c, const char* path, int64_t* n) {
+  if (!c || !path || !path[0]) return C2D_E_ARG;
+  if (!c->obs_ready) return fail(c, C2D_E_STATE, "c2d_obs_begin must precede c2d_obs_accumulate_file");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  return events_parse(c, path, obs_file_sink, c, n);
+}
+
+static int obs_set_file_sink(void* user, const double* ev, int64_t n, int on_device) {
+  c2d_ctx* c = static_cast<c2d_ctx*>(user);
+  return on_device ? obs_set_launch_sync(c, &ev, &n, 1) : c2d_obs_set_accumulate(c, ev, n);
+}
+
+extern "C" int c2d_obs_set_accumulate_file(c2d_ctx* c, const char* path, int64_t* n) {
+  if (!c || !path || !path[0]) return C2D_E_ARG;
+  if (c->oset.n < 1) return fail(c, C2D_E_STATE, "c2d_obs_set_accumulate_file: the set is empty");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  { const int rc = obs_settle(c); if (rc) return rc; }
+  c->oset_started = true;
+  return events_parse(c, path, obs_set_file_sink, c, n);
+}
+
+extern "C" int c2d_last_events_read_ms(c2d_ctx* c, double* io_ms, double* wait_ms, double* kernel_ms,
+                                       double* host_parse_ms, int64_t* canonical, int64_t* host_parsed,
+                                       int64_t* exact_fields, int32_t* chunks) {
+  if (!c) return C2D_E_ARG;
+  if (io_ms) *io_ms = c->evr_times.io_ms;
+  if (wait_ms) *wait_ms = c->evr_times.wait_ms;
+  if (kernel_ms) *kernel_ms = c->evr_times.kernel_ms;
+  if (host_parse_ms) *host_parse_ms = c->evr_times.host_parse_ms;
+  if (canonical) *canonical = c->evr_times.canonical;
+  if (host_parsed) *host_parsed = c->evr_times.host_parsed;
+  if (exact_fields) *exact_fields = c->evr_times.exact_fields;
+  if (chunks) *chunks = c->evr_times.chunks;
   return C2D_OK;
 }

@@ -81,6 +81,17 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_last_events_write_ms.restype = C.c_int
     lib.c2d_last_events_write_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int64)] * 2 + [
         C.POINTER(C.c_int32)]
+    lib.c2d_events_read.restype = C.c_int
+    lib.c2d_events_read.argtypes = [vp, C.c_char_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+    lib.c2d_obs_accumulate_file.restype = C.c_int
+    lib.c2d_obs_accumulate_file.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    lib.c2d_obs_set_accumulate_file.restype = C.c_int
+    lib.c2d_obs_set_accumulate_file.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    lib.c2d_last_events_read_ms.restype = C.c_int
+    lib.c2d_last_events_read_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int64)] * 3 + [
+        C.POINTER(C.c_int32)]
+    lib.c2d_selftest_scan.restype = C.c_int
+    lib.c2d_selftest_scan.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     lib.c2d_selftest_fmt.restype = C.c_int
     lib.c2d_selftest_fmt.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_char_p]
     lib.c2d_census_count.restype = C.c_int
@@ -500,6 +511,68 @@ class Engine:
         return {"scan_ms": d[0].value, "kernel_ms": d[1].value, "wait_ms": d[2].value, "io_ms": d[3].value,
                 "ambiguous": amb.value, "multilimb": ml.value, "chunks": chunks.value}
 
+    # -- the escape-event file read back, parsed on the device ----------------
+    def _check_records(self, rc: int, n) -> int:
+        """Like _check; the error carries the records delivered before it."""
+        if rc != 0:
+            e = C2DError(rc, self.lib.c2d_last_error(self.ctx).decode())
+            e.records = n.value
+            raise e
+        return n.value
+
+    def events_read(self, path, device: bool = False):
+        """The events [n, 7] of the event file `path` (c2d_events_read): a
+        numpy array, or with device=True a float64 torch tensor on this
+        context's GPU.  Canonical records are parsed by a kernel, the rest of
+        the file by the library's host parser."""
+        def buffer(m):
+            if device:
+                import torch
+                t = torch.empty((m, abi.EVENT_WORDS), dtype=torch.float64, device="cuda:%d" % self.grid.device)
+                return t, t.data_ptr()
+            a = np.empty((m, abi.EVENT_WORDS))
+            return a, a.ctypes.data
+
+        n = C.c_int64()
+        try:
+            cap = os.path.getsize(path) // 105 + 1      # a canonical file's records: one pass
+        except OSError:
+            cap = 1                                     # the library reports what is wrong with the file
+        while True:
+            out, ptr = buffer(cap)
+            self._check_records(self.lib.c2d_events_read(self.ctx, os.fsencode(path), C.c_void_p(ptr), cap,
+                                                         int(bool(device)), C.byref(n)), n)
+            if n.value <= cap:
+                return out[:n.value]
+            cap = n.value                                # free format: more records than 105-byte slots
+
+    def events_read_into(self, path, out) -> int:
+        """Parse `path` into `out` (numpy [cap, 7] float64, or a cuda float64
+        tensor): the first min(cap, n) records are stored; returns n."""
+        n = C.c_int64()
+        if hasattr(out, "data_ptr"):
+            assert out.is_cuda and out.dtype.itemsize == 8 and out.is_floating_point() and out.is_contiguous()
+            ptr, cap, dev = out.data_ptr(), out.numel() // abi.EVENT_WORDS, 1
+        else:
+            assert out.dtype == np.float64 and out.flags.c_contiguous
+            ptr, cap, dev = out.ctypes.data, out.size // abi.EVENT_WORDS, 0
+        return self._check_records(self.lib.c2d_events_read(self.ctx, os.fsencode(path), C.c_void_p(ptr if cap else None),
+                                                            cap, dev, C.byref(n)), n)
+
+    def last_events_read(self) -> dict:
+        """Timings and counts of the last events_read / obs*_accumulate_file
+        (c2d_last_events_read_ms)."""
+        d = [C.c_double() for _ in range(4)]
+        k = [C.c_int64() for _ in range(3)]
+        chunks = C.c_int32()
+        self._check(self.lib.c2d_last_events_read_ms(self.ctx, *[C.byref(v) for v in d], *[C.byref(v) for v in k],
+                                                     C.byref(chunks)))
+        return {"io_ms": d[0].value, "wait_ms": d[1].value, "kernel_ms": d[2].value, "host_parse_ms": d[3].value,
+                "canonical": k[0].value, "host_parsed": k[1].value, "exact_fields": k[2].value,
+                "chunks": chunks.value}
+
+    last_events_read_ms = last_events_read
+
     # -- observer-frame binning (postprocessing/pspt.c, plcm.c) ---------------
     def obs_begin(self, binning) -> None:
         """Zero a device histogram for `binning` (observer.Binning)."""
@@ -520,6 +593,13 @@ class Engine:
         """Bin n events at device address `ptr` (e.g. tensor.data_ptr() of a
         cuda float64 [n, 7] tensor on this context's GPU)."""
         self._check(self.lib.c2d_obs_accumulate_device(self.ctx, C.c_void_p(ptr), n))
+
+    def obs_accumulate_file(self, path) -> int:
+        """Bin the event file `path`, chunk by chunk as the device parses it
+        (c2d_obs_accumulate_file); returns the records binned.  A C2DError
+        carries them as .records."""
+        n = C.c_int64()
+        return self._check_records(self.lib.c2d_obs_accumulate_file(self.ctx, os.fsencode(path), C.byref(n)), n)
 
     def obs_result(self):
         """Raw sums (F = sum ew, F2 = sum ew^2, count), each [n_t, n_mu, n_e],
@@ -578,6 +658,12 @@ class Engine:
     def obs_set_accumulate_device(self, ptr: int, n: int) -> None:
         """Bin n events at device address `ptr` into every member."""
         self._check(self.lib.c2d_obs_set_accumulate_device(self.ctx, C.c_void_p(ptr), n))
+
+    def obs_set_accumulate_file(self, path) -> int:
+        """Bin the event file `path` into every member, chunk by chunk as the
+        device parses it; returns the records binned."""
+        n = C.c_int64()
+        return self._check_records(self.lib.c2d_obs_set_accumulate_file(self.ctx, os.fsencode(path), C.byref(n)), n)
 
     def obs_set_shape(self, member: int):
         """(n_t, n_mu, n_e, lds_rows) of a member: its histogram shape and
@@ -691,3 +777,19 @@ def device_fmt_e14_7(x: np.ndarray, device: int = 0) -> np.ndarray:
     if rc != 0:
         raise C2DError(rc, "c2d_selftest_fmt failed")
     return np.frombuffer(out.raw[:14 * x.size], np.uint8).reshape(-1, 14)
+
+
+def device_scan_e14_7(fields, device: int = 0):
+    """Parse 14-byte E14.7 fields (bytes of length 14 n, or a uint8 array
+    [n, 14]) on the GPU (c2d_selftest_scan): (bits uint64 [n], status int32
+    [n]); a field that is not canonical has status -1 and bits 0."""
+    lib = load_library()
+    text = fields if isinstance(fields, (bytes, bytearray)) else np.ascontiguousarray(fields, np.uint8).tobytes()
+    assert len(text) % 14 == 0
+    n = len(text) // 14
+    out = np.zeros(n, np.float64)
+    st = np.zeros(n, np.int32)
+    rc = lib.c2d_selftest_scan(device, bytes(text), n, out.ctypes.data_as(abi.PD), st.ctypes.data_as(abi.PI32))
+    if rc != 0:
+        raise C2DError(rc, "c2d_selftest_scan failed")
+    return out.view(np.uint64), st

@@ -289,8 +289,13 @@ def write_events(path, ev: np.ndarray, engine=None) -> None:
             f.write(" ".join(fortran_e14_7(v) for v in row) + "\n")
 
 
-def read_events(path) -> np.ndarray:
-    """fscanf("%lf" x 7) over the whole file, pspt.c:240-245."""
+def read_events(path, engine=None) -> np.ndarray:
+    """fscanf("%lf" x 7) over the whole file, pspt.c:240-245; with an engine
+    the library parses it on the GPU (Engine.events_read): the same values
+    bit for bit, and the E-less three-digit-exponent fields, which float()
+    does not take, as the numbers that were written."""
+    if engine is not None:
+        return engine.events_read(path)
     with open(path) as f:
         vals = np.array(f.read().split(), dtype=np.float64)
     return vals[: len(vals) // 7 * 7].reshape(-1, 7)
@@ -348,6 +353,28 @@ def bin_events(engine, binning: Binning, events: Iterable[Optional[np.ndarray]])
         engine.obs_accumulate(ev)
     F, F2, cnt, ms = engine.obs_result()
     return Histogram(F, F2, cnt, ms)
+
+
+def bin_event_files(engine, binning: Binning, files: Iterable) -> Histogram:
+    """Histogram event files on the engine's GPU: each is parsed on the
+    device chunk by chunk and binned from device memory
+    (c2d_obs_accumulate_file)."""
+    engine.obs_begin(binning)
+    for f in files:
+        engine.obs_accumulate_file(f)
+    F, F2, cnt, ms = engine.obs_result()
+    return Histogram(F, F2, cnt, ms)
+
+
+def bin_event_files_set(engine, binnings: Sequence[Binning], files: Iterable) -> List[Histogram]:
+    """Histogram event files into every binning of `binnings`, one pass over
+    each file (c2d_obs_set_accumulate_file)."""
+    engine.obs_set_clear()
+    ids = [engine.obs_set_add(b) for b in binnings]
+    for f in files:
+        engine.obs_set_accumulate_file(f)
+    ms, _ = engine.obs_set_kernel_ms()
+    return [Histogram(*engine.obs_set_result(i), ms) for i in ids]
 
 
 def bin_events_set(engine, binnings: Sequence[Binning],
@@ -487,7 +514,7 @@ def run_tool(tool: str, deck: str, directory=".", device: int = 0) -> List[Path]
     files, factor = event_files(b.infile, directory)
     eng = obs_engine(device)
     try:
-        h = bin_events(eng, b, (read_events(f) for f in files))
+        h = bin_event_files(eng, b, files)
     finally:
         eng.close()
     d = Path(directory)
@@ -514,7 +541,7 @@ def run_tools(tools: Sequence[Tuple[str, str]], directory=".", device: int = 0) 
     try:
         for infile, members in series.items():
             files, factor = event_files(infile, directory)
-            hs = bin_events_set(eng, [bins[i] for i in members], (read_events(f) for f in files))
+            hs = bin_event_files_set(eng, [bins[i] for i in members], files)
             for i, h in zip(members, hs):
                 if tools[i][0] == "pspt":
                     write_sed(d / bins[i].outfiles[0], bins[i], h, factor)

@@ -13,6 +13,7 @@
  *   src/xec2d.f:325/371  xec_add/graphics_collect  c2d_tally_device_ptr + one all-reduce
  *   src/update2d.f:1929  cens_add_up (REDUCE)      c2d_tally_device_ptr + one all-reduce
  *   src/imcleak2d.f:171  event-file writes         c2d_events, c2d_events_write
+ *   postprocessing/pspt.c:245  event-file reads     c2d_events_read, c2d_obs_accumulate_file
  *   src/census2d.f:1-76  write_cens/read_cens      c2d_census_export / c2d_census_import
  *   src/update2d.f:7     update (FP_calc, tridag,  c2d_fp_set_config + c2d_fp_step
  *     E_add_up, FP_send_job/recv_result)
@@ -421,6 +422,35 @@ int  c2d_events_write_from(c2d_ctx* ctx, const double* events, int64_t n, int32_
  * multi-limb path, and the chunk count.  Any pointer may be NULL. */
 int  c2d_last_events_write_ms(c2d_ctx* ctx, double* scan_ms, double* kernel_ms, double* wait_ms,
                               double* io_ms, int64_t* ambiguous, int64_t* multilimb, int32_t* chunks);
+/* The inverse: the text of an event file back to events (7 f64 a record),
+ * parsed on the device.  Stores the first min(cap, *n) records at buf, in
+ * host memory or (on_device != 0) in device memory on this context's GPU;
+ * *n = the records of the file; buf == NULL with cap == 0 only counts.
+ * Canonical records (105 bytes: seven right-justified 14-byte fields
+ * [ -]0.dddddddE[+-]dd or [ -]0.ddddddd[+-]ddd, one blank between them, a
+ * newline at the end) are parsed by a kernel, each field to the double
+ * nearest to its value, ties to even: the bits of strtod of the field (the
+ * E-less three-digit-exponent form, which fscanf("%lf") would split in two,
+ * is read as the number that was written).  From the first record that is not
+ * canonical to the end of the file, and for a tail shorter than a record, a
+ * host parser takes over: blank-separated tokens (canonical fields, else
+ * strtod of the whole token: free format, CRLF, NaN and Infinity), grouped in
+ * sevens, a trailing group of fewer dropped.  A token neither accepts gives
+ * C2D_E_IO with its byte offset in the message; the records before it have
+ * been delivered and *n counts them (the file is streamed in chunks of
+ * C2D_EVTEXT_CHUNK events through two pinned buffers, not validated first:
+ * memory is bounded by the chunk, not by the file).  C2D_E_IO also if the
+ * file cannot be opened or read; an empty file is 0 records. */
+int  c2d_events_read(c2d_ctx* ctx, const char* path, double* buf, int64_t cap, int32_t on_device, int64_t* n);
+/* Diagnostics of the last c2d_events_read / c2d_obs_accumulate_file /
+ * c2d_obs_set_accumulate_file: host milliseconds in read(), waiting for a
+ * chunk's copy and parse kernel, device milliseconds of the parse kernels,
+ * host milliseconds of the host parser; records parsed on the device and on
+ * the host, fields the device decided by the multi-limb path, device chunks.
+ * Any pointer may be NULL. */
+int  c2d_last_events_read_ms(c2d_ctx* ctx, double* io_ms, double* wait_ms, double* kernel_ms,
+                             double* host_parse_ms, int64_t* canonical, int64_t* host_parsed,
+                             int64_t* exact_fields, int32_t* chunks);
 
 /* Census held on the device for the next step. */
 int  c2d_census_count(c2d_ctx* ctx, int64_t* n);
@@ -508,6 +538,11 @@ int  c2d_obs_accumulate(c2d_ctx* ctx, const double* events, int64_t n);
 /* Same for n events already in device memory on the context's GPU (e.g. a
  * gathered event buffer or a torch tensor); no copy. */
 int  c2d_obs_accumulate_device(c2d_ctx* ctx, const double* d_events, int64_t n);
+/* The same over an event file (c2d_events_read's parser): each chunk is
+ * binned from device memory as it is parsed; *n = the records binned (n may
+ * be NULL), also when the call fails on a bad token (C2D_E_IO).  Synchronous
+ * on return.  C2D_E_STATE without c2d_obs_begin. */
+int  c2d_obs_accumulate_file(c2d_ctx* ctx, const char* path, int64_t* n);
 /* Download the raw sums ([n_t][n_mu][n_e] each; any pointer may be NULL)
  * and the device time of the binning launches so far (ms). */
 int  c2d_obs_result(c2d_ctx* ctx, double* F, double* F2, double* count, double* kernel_ms);
@@ -555,6 +590,9 @@ int  c2d_obs_set_add_plcm(c2d_ctx* ctx, const char* deck, int32_t* id);
 int  c2d_obs_set_accumulate(c2d_ctx* ctx, const double* events, int64_t n);
 /* Same for n events already in device memory on the context's GPU. */
 int  c2d_obs_set_accumulate_device(c2d_ctx* ctx, const double* d_events, int64_t n);
+/* The same over an event file, as c2d_obs_accumulate_file; C2D_E_STATE on an
+ * empty set. */
+int  c2d_obs_set_accumulate_file(c2d_ctx* ctx, const char* path, int64_t* n);
 /* A member's histogram shape and how many of its leading time rows the
  * kernel keeps in LDS (the rest use global atomics); any pointer may be NULL. */
 int  c2d_obs_set_shape(c2d_ctx* ctx, int32_t id, int32_t* n_t, int32_t* n_mu, int32_t* n_e, int32_t* lds_rows);
@@ -656,6 +694,12 @@ int  c2d_selftest_mcd_fast(int device, const double* z, int n, double* out);
  * C2D_FMT_SELFTEST_MULTILIMB=1 (environment, read at every call) sends every
  * value the fast path cannot decide through the multi-limb path. */
 int  c2d_selftest_fmt(int device, const double* x, int64_t n, char* out);
+/* Diagnostics: n 14-byte E14.7 fields at text + 14 i parsed on the GPU
+ * (csrc/c2d_scan.h as the event reader runs it): status[i] = 0, 1 (decided by
+ * the multi-limb path) or -1 (not canonical; out[i] is then left as it was).
+ * C2D_SCAN_SELFTEST_EXACT=1 (environment, read at every call; the event
+ * reader honours it too) sends every field through the multi-limb path. */
+int  c2d_selftest_scan(int device, const char* text, int64_t n, double* out, int32_t* status);
 
 #ifdef __cplusplus
 }

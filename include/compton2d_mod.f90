@@ -251,6 +251,38 @@ module compton2d
        integer(c_int32_t), value :: append
      end function c2d_events_write_from
 
+     ! an event file back to events, parsed on the device: the first
+     ! min(cap, n) records to buf (c_loc of a host array, or a device
+     ! address with on_device /= 0); n = the records of the file
+     integer(c_int) function c2d_events_read(ctx, path, buf, cap, on_device, n) &
+          bind(C, name='c2d_events_read')
+       import :: c_int, c_ptr, c_char, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       type(c_ptr), value :: buf
+       integer(c_int64_t), value :: cap
+       integer(c_int32_t), value :: on_device
+       integer(c_int64_t), intent(out) :: n
+     end function c2d_events_read
+
+     ! bin an event file chunk by chunk as it is parsed (after c2d_obs_begin)
+     integer(c_int) function c2d_obs_accumulate_file(ctx, path, n) &
+          bind(C, name='c2d_obs_accumulate_file')
+       import :: c_int, c_ptr, c_char, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int64_t), intent(out) :: n
+     end function c2d_obs_accumulate_file
+
+     integer(c_int) function c2d_last_events_read_ms(ctx, io_ms, wait_ms, kernel_ms, host_parse_ms, &
+          canonical, host_parsed, exact_fields, chunks) bind(C, name='c2d_last_events_read_ms')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: io_ms, wait_ms, kernel_ms, host_parse_ms
+       integer(c_int64_t), intent(out) :: canonical, host_parsed, exact_fields
+       integer(c_int32_t), intent(out) :: chunks
+     end function c2d_last_events_read_ms
+
      integer(c_int) function c2d_census_count(ctx, n) bind(C, name='c2d_census_count')
        import :: c_int, c_ptr, c_int64_t
        type(c_ptr), value :: ctx
@@ -388,6 +420,14 @@ module compton2d
        type(c_ptr), value :: ctx, d_events         ! device address of n events
        integer(c_int64_t), value :: n
      end function c2d_obs_set_accumulate_device
+
+     integer(c_int) function c2d_obs_set_accumulate_file(ctx, path, n) &
+          bind(C, name='c2d_obs_set_accumulate_file')
+       import :: c_int, c_ptr, c_char, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int64_t), intent(out) :: n
+     end function c2d_obs_set_accumulate_file
 
      integer(c_int) function c2d_obs_set_shape(ctx, id, n_t, n_mu, n_e, lds_rows) &
           bind(C, name='c2d_obs_set_shape')
