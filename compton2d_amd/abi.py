@@ -341,7 +341,12 @@ class StepInputs:
 C2D_E_FP = -8
 C2D_E_NONFINITE = -11
 C2D_E_STATE = -7
-C2D_E_IO = -10          # c2d_events_write*, c2d_events_read, c2d_obs*_accumulate_file
+C2D_E_IO = -10          # c2d_events_write*, c2d_events_read, c2d_obs*_accumulate_file, c2d_census_write*/_read*
+C2D_E_ARG = -1
+C2D_E_CENSUS_OVERFLOW = -3
+# the census record file (c2d_census_write / c2d_census_read; csrc/c2d_censfmt.h)
+CENSUS_FILE_RECORD = 116        # bytes: (6e14.7), newline, (6i5), newline
+CENSUS_KEYS_SUFFIX = ".keys"    # little-endian u64 lineage keys, one a record
 ERRORS[C2D_E_FP] = "C2D_E_FP"
 FP_E_OLD, FP_E_NEW, FP_HR, FP_HR_ST, FP_DELTA_T, FP_STEPS, FP_SKIPPED = range(7)
 FP_NDIAG = 8

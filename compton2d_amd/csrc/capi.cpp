@@ -22,6 +22,8 @@
 #include "c2d_rng.h"
 #include "pspt_host.h"
 #include "plcm_host.h"
+#include "c2d_censfmt.h"
+#include "c2d_censtext.hpp"
 #include "c2d_evparse.hpp"
 #include "c2d_evtext.hpp"
 
@@ -201,6 +203,10 @@ struct c2d_ctx {
   c2d_evt_times evt_times = {};         /* of the last c2d_events_write* */
   c2d_evt_reader* evr = nullptr;        /* c2d_events_read's staging buffers (evparse.hip) */
   c2d_evr_times evr_times = {};         /* of the last c2d_events_read / c2d_obs*_accumulate_file */
+  c2d_cens_file* cfile = nullptr;       /* the census file calls' staging buffers (censtext.hip) */
+  c2d_cens_times cens_times = {};       /* of the last c2d_census_write* / c2d_census_read* */
+  unsigned long long* cens_bad = nullptr;   /* c2d_census_read: the first record out of range */
+  hipEvent_t cens_ev[2] = {nullptr, nullptr};
   /* the context's own escapes binned on a second stream (c2d_obs_accumulate
    * with no events): it overlaps the next step's FP / tables / sources, and
    * the next generation-0 launch, which rewrites the event buffer, waits
@@ -316,7 +322,7 @@ extern "C" const char* c2d_last_error(c2d_ctx* ctx) { return ctx ? ctx->err.c_st
 /* Geo bucket tables of grid_lookup (c2d_device.hpp): bucket b holds the
  * bin (smallest i in [1, n] with x < E[i+1], the bisection's answer) of the
  * smallest double whose top 16 bits are k0 + b. */
-static int grid_bin_host(const double* E, int n, double x) {
+static __host__ __device__ int grid_bin_host(const double* E, int n, double x) {
   int lo = 1, hi = n;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -554,6 +560,10 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
   if (c->mono_flag) (void)hipFree(c->mono_flag);
   c2d_evtext_free(c->evt);
   c2d_evparse_free(c->evr);
+  c2d_censtext_free(c->cfile);
+  if (c->cens_bad) (void)hipFree(c->cens_bad);
+  for (hipEvent_t e : c->cens_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   void* ptrs[] = {c->geo, c->gnt, c->kappa_cur, c->kappa_prev, c->eps_tot, c->eps_th, c->f_nt,
                   c->Pnt, c->n_e, c->vfrac, c->ewsv, c->surf_ew, c->surf_tbb, c->tbbl,
@@ -1785,7 +1795,7 @@ extern "C" int c2d_events(c2d_ctx* c, double* buf, int64_t cap, int64_t* n) {
  * decodes to 0.0, so an import of phi = 0 exports 0. */
 static constexpr double C2D_PI_REF = 3.1415926536;   /* general.pa:24 */
 static inline bool cens_encoded(const c2d_ctx* c) { return c->cfg.comtot_mode == C2D_COMTOT_TABLE; }
-static inline double cens_phi_decode(double eta, uint32_t bins) {
+static __host__ __device__ inline double cens_phi_decode(double eta, uint32_t bins) {
   if (eta == 1.0 && (bins & C2D_CENS_ESW)) return 0.0;
   const double ph = c2d_acos(eta);
   return (bins & C2D_CENS_ESW) ? 2.0 * C2D_PI_REF - ph : ph;
@@ -3411,5 +3421,272 @@ extern "C" int c2d_last_events_read_ms(c2d_ctx* c, double* io_ms, double* wait_m
   if (host_parsed) *host_parsed = c->evr_times.host_parsed;
   if (exact_fields) *exact_fields = c->evr_times.exact_fields;
   if (chunks) *chunks = c->evr_times.chunks;
+  return C2D_OK;
+}
+
+/* ------------------------------------------------------------------------
+ * The census as a record file of write_cens / read_cens, formatted and
+ * parsed on the device (censtext.hip).  Here: the context's census to and
+ * from the plain records of the file, the device versions of the host loops
+ * of census_download and c2d_census_import.
+ * ---------------------------------------------------------------------- */
+/* packed records -> plain ones (d6 with phi decoded, the five integers, the key) */
+__global__ void __launch_bounds__(256) c2d_census_plain_kernel(const uint64_t* __restrict__ rec, int64_t n, int enc,
+                                                               double* __restrict__ d6, int32_t* __restrict__ i5,
+                                                               uint64_t* __restrict__ keys) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t* r = rec + i * C2D_CENSUS_REC_WORDS;
+    const uint32_t jk = (uint32_t)(r[6] & 0xffffffffull), bins = (uint32_t)(r[6] >> 32);
+    for (int f = 0; f < 6; f++) {
+      const double v = __longlong_as_double((long long)r[f]);
+      d6[6 * i + f] = (f == 3 && enc) ? cens_phi_decode(v, bins) : v;
+    }
+    i5[5 * i + 0] = (int32_t)(bins & 0xff);
+    i5[5 * i + 1] = (int32_t)((bins >> 8) & 0xff);
+    i5[5 * i + 2] = (int32_t)((bins >> 16) & 0xff);
+    i5[5 * i + 3] = (int32_t)c2d_cens_j(jk);
+    i5[5 * i + 4] = (int32_t)c2d_cens_k(jk);
+    keys[i] = r[7];
+  }
+}
+
+/* plain records -> packed ones, as c2d_census_import forms them; a record out
+ * of range lowers *first_bad and is not stored */
+__global__ void __launch_bounds__(256) c2d_census_encode_kernel(const double* __restrict__ d6,
+                                                                const int32_t* __restrict__ i5,
+                                                                const uint64_t* __restrict__ keys, int64_t n,
+                                                                const Geo* __restrict__ geo, double egg_min, int nz,
+                                                                int nr, int enc, uint64_t* __restrict__ rec,
+                                                                unsigned long long* first_bad) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t* q = i5 + 5 * i;
+    if (q[3] < 1 || q[3] > nz || q[4] < 1 || q[4] > nr || q[0] < 0 || q[0] > 255 || q[1] < 0 || q[1] > 255 ||
+        q[2] < 0 || q[2] > 255) {
+      atomicMin(first_bad, (unsigned long long)i);
+      continue;
+    }
+    uint32_t bins = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+    const double ph = d6[6 * i + 3], xnu = d6[6 * i + 5];
+    if (enc && !(ph <= C2D_PI_REF && ph >= 1.0e-10)) bins |= C2D_CENS_ESW;
+    uint64_t* r = rec + i * C2D_CENSUS_REC_WORDS;
+    for (int f = 0; f < 6; f++) r[f] = (uint64_t)__double_as_longlong((f == 3 && enc) ? c2d_cos(ph) : d6[6 * i + f]);
+    const int ie = grid_bin_host(geo->E_ph, C2D_N_VOL, xnu);
+    const int efl = xnu > egg_min ? grid_bin_host(geo->E_field, C2D_NPHFIELD, xnu) : 0;
+    r[6] = (uint64_t)c2d_cens_jk(q[3], q[4], ie, efl) | ((uint64_t)bins << 32);
+    r[7] = keys[i];
+  }
+}
+
+static int census_file_fail(c2d_ctx* c, int rc, const char* err) {
+  /* a callback that failed has left its own message */
+  return rc ? (err[0] ? fail(c, rc, "%s", err) : rc) : C2D_OK;
+}
+
+/* records [first, first + n) of the census as plain records, on the stream */
+static int census_write_source(void* user, int64_t first, int64_t n, double* d6, int32_t* i5, uint64_t* keys) {
+  c2d_ctx* c = static_cast<c2d_ctx*>(user);
+  { const int rc = ensure_tmp(c, n); if (rc) return rc; }
+  const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)c->n_cu * 8);
+  hipLaunchKernelGGL(c2d_census_pack_kernel, dim3(g), dim3(256), 0, c->stream, c->cens[c->cur].soa(), cens_list(c),
+                     first, (int64_t)1, n, c->tmp_rec);
+  hipLaunchKernelGGL(c2d_census_plain_kernel, dim3(g), dim3(256), 0, c->stream, c->tmp_rec, n,
+                     cens_encoded(c) ? 1 : 0, d6, i5, keys);
+  HIPCHK(c, hipGetLastError());
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_write(c2d_ctx* c, const char* path, int64_t* n_written) {
+  if (!c || !path || !path[0]) return C2D_E_ARG;
+  if (c->census_lost) return census_lost(c, "c2d_census_write");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  char err[768] = "";
+  const int rc = c2d_censtext_write(&c->cfile, c->cfg.device, c->stream, census_write_source, c, nullptr, nullptr,
+                                    nullptr, c->n_census, path, &c->cens_times, err, sizeof err);
+  if (!rc && n_written) *n_written = c->n_census;
+  return census_file_fail(c, rc, err);
+}
+
+extern "C" int c2d_census_write_from(c2d_ctx* c, const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
+                                     const char* path) {
+  if (!c || !path || !path[0] || n < 0 || (n > 0 && (!d6 || !i5 || !keys))) return C2D_E_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  char err[768] = "";
+  const int rc = c2d_censtext_write(&c->cfile, c->cfg.device, c->stream, nullptr, nullptr, d6, i5, keys, n, path,
+                                    &c->cens_times, err, sizeof err);
+  return census_file_fail(c, rc, err);
+}
+
+namespace {
+struct CensRecDst {     /* c2d_census_read_records */
+  c2d_ctx* c;
+  double* d6;
+  int32_t* i5;
+  uint64_t* keys;
+  int64_t cap, done;
+};
+struct CensStoreDst {   /* c2d_census_read */
+  c2d_ctx* c;
+  bool storing;         /* the previous census is gone */
+  int64_t base;         /* records handed over so far */
+};
+}  // namespace
+
+static int census_records_sink(void* user, const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
+                               int on_device) {
+  CensRecDst* d = static_cast<CensRecDst*>(user);
+  const int64_t m = std::min(n, d->cap - d->done);
+  if (m <= 0) return C2D_OK;
+  if (on_device) {
+    /* on the context's stream, behind the parse kernel; waited for, because the staging buffers are reused */
+    hipStream_t s = d->c->stream;
+    HIPCHK(d->c, hipMemcpyAsync(d->d6 + 6 * d->done, d6, (size_t)m * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(d->c, hipMemcpyAsync(d->i5 + 5 * d->done, i5, (size_t)m * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(d->c, hipMemcpyAsync(d->keys + d->done, keys, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(d->c, hipStreamSynchronize(s));
+  } else {
+    memcpy(d->d6 + 6 * d->done, d6, (size_t)m * 6 * sizeof(double));
+    memcpy(d->i5 + 5 * d->done, i5, (size_t)m * 5 * sizeof(int32_t));
+    memcpy(d->keys + d->done, keys, (size_t)m * sizeof(uint64_t));
+  }
+  d->done += m;
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_read_records(c2d_ctx* c, const char* path, double* d6, int32_t* i5, uint64_t* keys,
+                                       int64_t cap, int64_t* n) {
+  if (!c || !path || !path[0] || !n || cap < 0 || (cap > 0 && (!d6 || !i5 || !keys))) return C2D_E_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  CensRecDst d = {c, d6, i5, keys, cap, 0};
+  char err[768] = "";
+  const int rc = c2d_censtext_read(&c->cfile, c->cfg.device, c->stream, path, cap > 0 ? census_records_sink : nullptr,
+                                   &d, n, &c->cens_times, err, sizeof err);
+  return census_file_fail(c, rc, err);
+}
+
+/* n plain records (device memory) behind the census, through c2d_census_append */
+static int census_store(c2d_ctx* c, CensStoreDst* d, const double* d6, const int32_t* i5, const uint64_t* keys,
+                        int64_t n) {
+  if (!d->storing) {   /* the first records: the file's census replaces the context's */
+    d->storing = true;
+    c->n_census = 0;
+    if (c->chunked) c->n_clist = 0;
+    c->census_lost = false;
+  }
+  if (c->n_census + n > c->cfg.census_capacity)
+    return fail(c, C2D_E_CENSUS_OVERFLOW, "c2d_census_read: more than %lld records (census_capacity)",
+                (long long)c->cfg.census_capacity);
+  { const int rc = ensure_tmp(c, n); if (rc) return rc; }
+  if (!c->cens_bad) {
+    HIPCHK(c, hipMalloc((void**)&c->cens_bad, sizeof(unsigned long long)));
+    for (hipEvent_t& e : c->cens_ev) HIPCHK(c, hipEventCreate(&e));
+  }
+  unsigned long long bad = ~0ull;
+  HIPCHK(c, hipMemsetAsync(c->cens_bad, 0xff, sizeof bad, c->stream));
+  const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)c->n_cu * 8);
+  HIPCHK(c, hipEventRecord(c->cens_ev[0], c->stream));
+  hipLaunchKernelGGL(c2d_census_encode_kernel, dim3(g), dim3(256), 0, c->stream, d6, i5, keys, n, c->geo, c->egg_min,
+                     c->nz, c->nr, cens_encoded(c) ? 1 : 0, c->tmp_rec, c->cens_bad);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->cens_ev[1], c->stream));
+  HIPCHK(c, hipMemcpyAsync(&bad, c->cens_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->cens_ev[0], c->cens_ev[1]);
+  c->cens_times.conv_ms += ms;
+  if (bad != ~0ull) return fail(c, C2D_E_ARG, "census record %lld out of range", (long long)(d->base + (int64_t)bad));
+  d->base += n;
+  return c2d_census_append(c, c->tmp_rec, n);
+}
+
+static int census_store_sink(void* user, const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
+                             int on_device) {
+  CensStoreDst* d = static_cast<CensStoreDst*>(user);
+  c2d_ctx* c = d->c;
+  if (on_device) return census_store(c, d, d6, i5, keys, n);
+  /* the host parser's records: staged on the device for the same kernel */
+  double* a = nullptr;
+  int32_t* b = nullptr;
+  uint64_t* k = nullptr;
+  int rc = C2D_OK;
+  if (hipMalloc((void**)&a, (size_t)n * 6 * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&b, (size_t)n * 5 * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc((void**)&k, (size_t)n * sizeof(uint64_t)) != hipSuccess ||
+      hipMemcpy(a, d6, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(b, i5, (size_t)n * 5 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(k, keys, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(c, C2D_E_HIP, "c2d_census_read: staging %lld host-parsed records: %s", (long long)n,
+              hipGetErrorString(hipGetLastError()));
+  if (!rc) rc = census_store(c, d, a, b, k, n);
+  if (a) (void)hipFree(a);
+  if (b) (void)hipFree(b);
+  if (k) (void)hipFree(k);
+  return rc;
+}
+
+/* Records of a wholly canonical file, from its size: both newlines of the
+ * first and of the last record where canonical records have them (a file
+ * with CR LF line ends, say, can have a size that is a multiple of 116 too).
+ * -1 if the file does not look like one. */
+static int64_t canonical_records(const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return -1;
+  int64_t n = -1;
+  if (fseeko(f, 0, SEEK_END) == 0) {
+    const int64_t size = (int64_t)ftello(f);
+    if (size > 0 && size % C2D_CENS_RECORD == 0) {
+      bool ok = true;
+      for (int64_t off : {(int64_t)84, (int64_t)115, size - 32, size - 1})
+        ok = ok && fseeko(f, (off_t)off, SEEK_SET) == 0 && fgetc(f) == '\n';
+      if (ok) n = size / C2D_CENS_RECORD;
+    }
+  }
+  (void)fclose(f);
+  return n;
+}
+
+extern "C" int c2d_census_read(c2d_ctx* c, const char* path, int64_t* n) {
+  if (!c || !path || !path[0]) return C2D_E_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (canonical_records(path) > c->cfg.census_capacity)   /* before the census is touched */
+    return fail(c, C2D_E_CENSUS_OVERFLOW, "c2d_census_read: '%s' holds %lld records > capacity %lld", path,
+                (long long)canonical_records(path), (long long)c->cfg.census_capacity);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CensStoreDst d = {c, false, 0};
+  char err[768] = "";
+  int64_t got = 0;
+  c2d_cens_times T = {};
+  c->cens_times = T;   /* the sink adds its conversion time while the file is read */
+  int rc = c2d_censtext_read(&c->cfile, c->cfg.device, c->stream, path, census_store_sink, &d, &got, &T, err,
+                             sizeof err);
+  T.conv_ms = c->cens_times.conv_ms;
+  c->cens_times = T;
+  if (n) *n = rc ? 0 : got;
+  if (rc) {
+    rc = census_file_fail(c, rc, err);
+    if (d.storing) {   /* the previous census is gone and the file's is incomplete */
+      c->n_census = 0;
+      if (c->chunked) c->n_clist = 0;
+      c->census_lost = true;
+    }
+    return rc;
+  }
+  if (!d.storing) {    /* an empty file: an empty census */
+    c->n_census = 0;
+    if (c->chunked) c->n_clist = 0;
+    c->census_lost = false;
+  }
+  return C2D_OK;
+}
+
+extern "C" int c2d_last_census_file_ms(c2d_ctx* c, double* io_ms, double* wait_ms, double* kernel_ms, double* conv_ms,
+                                       int64_t* device_records, int64_t* host_records, int32_t* chunks) {
+  if (!c) return C2D_E_ARG;
+  if (io_ms) *io_ms = c->cens_times.io_ms;
+  if (wait_ms) *wait_ms = c->cens_times.wait_ms;
+  if (kernel_ms) *kernel_ms = c->cens_times.kernel_ms;
+  if (conv_ms) *conv_ms = c->cens_times.conv_ms;
+  if (device_records) *device_records = c->cens_times.device_records;
+  if (host_records) *host_records = c->cens_times.host_records;
+  if (chunks) *chunks = c->cens_times.chunks;
   return C2D_OK;
 }

@@ -94,6 +94,18 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_selftest_scan.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     lib.c2d_selftest_fmt.restype = C.c_int
     lib.c2d_selftest_fmt.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_char_p]
+    lib.c2d_census_write.restype = C.c_int
+    lib.c2d_census_write.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    lib.c2d_census_write_from.restype = C.c_int
+    lib.c2d_census_write_from.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p]
+    lib.c2d_census_read.restype = C.c_int
+    lib.c2d_census_read.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    lib.c2d_census_read_records.restype = C.c_int
+    lib.c2d_census_read_records.argtypes = [vp, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.POINTER(C.c_int64)]
+    lib.c2d_last_census_file_ms.restype = C.c_int
+    lib.c2d_last_census_file_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int64)] * 2 + [
+        C.POINTER(C.c_int32)]
     lib.c2d_census_count.restype = C.c_int
     lib.c2d_census_count.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.c2d_census_export.restype = C.c_int
@@ -357,6 +369,64 @@ class Engine:
         d6, i5, keys = census_io.read_census(path)
         self.import_census(d6, i5, keys)
         return len(keys)
+
+    # -- the census record file, written and read by the library -------------
+    def write_census_file(self, path) -> int:
+        """Write the device census to `path` and `<path>.keys`, formatted on
+        the device (c2d_census_write): the bytes save_census writes.  Returns
+        the records written; the census is unchanged."""
+        n = C.c_int64()
+        self._check(self.lib.c2d_census_write(self.ctx, os.fsencode(path), C.byref(n)))
+        return n.value
+
+    def write_census_records(self, d6, i5, keys, path) -> None:
+        """The same for records [n, 6], [n, 5], [n] of the caller, in the
+        layout of census() (c2d_census_write_from); nothing is checked against
+        the grid."""
+        d6 = np.ascontiguousarray(d6, np.float64).reshape(-1, 6)
+        i5 = np.ascontiguousarray(i5, np.int32).reshape(-1, 5)
+        keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+        n = len(keys)
+        assert len(d6) == n and len(i5) == n
+        self._check(self.lib.c2d_census_write_from(
+            self.ctx, C.c_void_p(d6.ctypes.data if n else None), C.c_void_p(i5.ctypes.data if n else None),
+            C.c_void_p(keys.ctypes.data if n else None), n, os.fsencode(path)))
+
+    def read_census_file(self, path) -> int:
+        """Replace the device census by the records of `path`, parsed and
+        converted on the device (c2d_census_read): what load_census does.
+        Returns the record count.  If the call fails after it has begun
+        storing, the census is lost as after a failed in-place step."""
+        n = C.c_int64()
+        self._check(self.lib.c2d_census_read(self.ctx, os.fsencode(path), C.byref(n)))
+        return n.value
+
+    def parse_census_file(self, path):
+        """(d6 [n, 6], i5 [n, 5], keys [n]) of the census record file `path`
+        (c2d_census_read_records): parsed only, the census is untouched."""
+        n = C.c_int64()
+        try:
+            cap = os.path.getsize(path) // 116 + 1      # a canonical file's records: one pass
+        except OSError:
+            cap = 1                                     # the library reports what is wrong with the file
+        while True:
+            d6, i5, keys = np.empty((cap, 6)), np.empty((cap, 5), np.int32), np.empty(cap, np.uint64)
+            self._check_records(self.lib.c2d_census_read_records(
+                self.ctx, os.fsencode(path), C.c_void_p(d6.ctypes.data), C.c_void_p(i5.ctypes.data),
+                C.c_void_p(keys.ctypes.data), cap, C.byref(n)), n)
+            if n.value <= cap:
+                return d6[:n.value], i5[:n.value], keys[:n.value]
+            cap = n.value                                # short lines: more records than 116-byte slots
+
+    def last_census_file(self) -> dict:
+        """Timings and counts of the last census file call (c2d_last_census_file_ms)."""
+        d = [C.c_double() for _ in range(4)]
+        k = [C.c_int64() for _ in range(2)]
+        chunks = C.c_int32()
+        self._check(self.lib.c2d_last_census_file_ms(self.ctx, *[C.byref(v) for v in d], *[C.byref(v) for v in k],
+                                                     C.byref(chunks)))
+        return {"io_ms": d[0].value, "wait_ms": d[1].value, "kernel_ms": d[2].value, "convert_ms": d[3].value,
+                "device_records": k[0].value, "host_records": k[1].value, "chunks": chunks.value}
 
     def last_kernel_ms(self):
         """(generation-0 kernel ms, all launches ms, launches) of the last step (HIP events)."""

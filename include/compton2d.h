@@ -14,7 +14,8 @@
  *   src/update2d.f:1929  cens_add_up (REDUCE)      c2d_tally_device_ptr + one all-reduce
  *   src/imcleak2d.f:171  event-file writes         c2d_events, c2d_events_write
  *   postprocessing/pspt.c:245  event-file reads     c2d_events_read, c2d_obs_accumulate_file
- *   src/census2d.f:1-76  write_cens/read_cens      c2d_census_export / c2d_census_import
+ *   src/census2d.f:1-76  write_cens/read_cens      c2d_census_write / c2d_census_read (the files),
+ *                                                  c2d_census_export / c2d_census_import (arrays)
  *   src/update2d.f:7     update (FP_calc, tridag,  c2d_fp_set_config + c2d_fp_step
  *     E_add_up, FP_send_job/recv_result)
  *
@@ -66,7 +67,7 @@ extern "C" {
                                        or NaN/Inf in n_field, ecens or the
                                        updated electron state                     */
 #define C2D_E_RCCL             -9   /* RCCL (communicator / all-reduce) error     */
-#define C2D_E_IO              -10   /* a file could not be written                */
+#define C2D_E_IO              -10   /* a file could not be written or read        */
 #define C2D_E_NONFINITE       -11   /* NaN/Inf in a table, a tally or an emission
                                        output (the reference would carry it on:
                                        NaN counts, a collapsed run)               */
@@ -474,6 +475,71 @@ int  c2d_census_truncate(c2d_ctx* ctx, int64_t n);
  * checkpoints in chunks, or a strided sample of a large census. */
 int  c2d_census_export_range(c2d_ctx* ctx, int64_t first, int64_t stride, double* d6,
                              int32_t* i5, uint64_t* keys, int64_t cap, int64_t* n);
+
+/* The census as the record file of write_cens / read_cens (census2d.f:1-76),
+ * formatted on the device: two lines a record, (6e14.7) rpre zpre wmu phi ew
+ * xnu and (6i5) jgpsp jgplc jgpmu jph kph seed, 116 bytes with their
+ * newlines and no separators; the sixth integer is key mod 100000 and the
+ * full 64-bit lineage keys go to `path`.keys (little-endian u64, one a
+ * record).  The records are those of c2d_census_export, in its order;
+ * *n_written = records written (n_written may be NULL).  The call returns
+ * when both files are complete and closed and leaves the census unchanged.
+ * Errors: C2D_E_STATE if the census was lost by a failed in-place step;
+ * C2D_E_NONFINITE if a record holds a NaN or Inf (the message names the
+ * first such record): the records are scanned before either file is opened,
+ * so both files are then exactly as they were; C2D_E_IO if a file cannot be
+ * opened or written.  An empty census gives two empty files.  The text is
+ * staged in chunks of C2D_CENSTEXT_CHUNK records (environment, read at every
+ * call; default 1048576) through two pinned host buffers: memory is bounded
+ * by the chunk, not by the census. */
+int  c2d_census_write(c2d_ctx* ctx, const char* path, int64_t* n_written);
+/* The same for n caller-supplied records in host memory, in the layout of
+ * c2d_census_export (d6 [n][6], i5 [n][5], keys [n]).  Nothing in the
+ * records is checked against the grid; an integer outside -9999..99999 is
+ * written as five asterisks, as Fortran's I5 does. */
+int  c2d_census_write_from(c2d_ctx* ctx, const double* d6, const int32_t* i5, const uint64_t* keys,
+                           int64_t n, const char* path);
+/* The inverse: replaces the context's census with the records of the file,
+ * parsed and converted on the device (what c2d_census_import does with host
+ * arrays); *n = the records of the file (n may be NULL).  Keys come from
+ * `path`.keys if it exists, else (a file written by the reference) they are
+ * derived from the seed column and the record index (splitmix64, as
+ * compton2d_amd/census_io.py derive_key).  Canonical records (116 bytes:
+ * fields [ -]0.dddddddE[+-]dd or [ -]0.ddddddd[+-]ddd, integers as blanks, an
+ * optional '-' and digits, both newlines in place) are parsed by a kernel,
+ * each double to the bits of strtod of its field.  From the first record
+ * that is not canonical to the end of the file, and for a tail shorter than
+ * a record, a host parser takes over: CR stripped, blank lines skipped,
+ * fixed 14- and 5-column fields, the E-less three-digit exponent repaired, D
+ * or a lower-case e as the exponent letter, a missing final newline
+ * accepted.  Errors: C2D_E_IO with the byte offset in the message for a
+ * field the host parser cannot read (asterisks included) and for an odd
+ * number of lines; C2D_E_IO if a file cannot be opened or read or `path`.keys
+ * does not hold 8 bytes a record; C2D_E_ARG for a record out of range, as in
+ * c2d_census_import; C2D_E_CENSUS_OVERFLOW if the file holds more records
+ * than census_capacity: for a wholly canonical file this is decided from
+ * the file's size before the census is touched.  A call that fails after it
+ * has begun storing leaves the census lost, as a failed in-place step does:
+ * the count is 0 and census reads and c2d_run_step return C2D_E_STATE until
+ * the next c2d_census_import, c2d_census_read or c2d_census_truncate.  A
+ * call that fails before that (a file that cannot be opened) leaves the
+ * census as it was.  An empty file is a census of 0 records. */
+int  c2d_census_read(c2d_ctx* ctx, const char* path, int64_t* n);
+/* Parses only: the first min(cap, *n) records into host arrays in the layout
+ * of c2d_census_export; *n = the records of the file; NULL buffers with
+ * cap == 0 only count.  The context's census is untouched. */
+int  c2d_census_read_records(c2d_ctx* ctx, const char* path, double* d6, int32_t* i5, uint64_t* keys,
+                             int64_t cap, int64_t* n);
+/* Diagnostics of the last c2d_census_write* / c2d_census_read*: host
+ * milliseconds in file I/O and waiting for chunks, device milliseconds of
+ * the format or parse kernels and of the record conversion kernels (write:
+ * both passes over the census, the non-finite scan included; 0 for
+ * caller-supplied records and for c2d_census_read_records), records parsed
+ * on the device and on the host (0 after a write), and the chunk count.
+ * Any pointer may be NULL. */
+int  c2d_last_census_file_ms(c2d_ctx* ctx, double* io_ms, double* wait_ms, double* kernel_ms,
+                             double* convert_ms, int64_t* device_records, int64_t* host_records,
+                             int32_t* chunks);
 
 /* Batched tridiagonal (Thomas with the reference's clipping) solve: one
  * zone per wavefront.  x is [ncell][nt] on the host. */

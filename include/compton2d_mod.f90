@@ -310,6 +310,57 @@ module compton2d
        integer(c_int64_t), value :: n
      end function c2d_census_import
 
+     ! the census as the record file of write_cens (and path.keys),
+     ! formatted on the device; n_written = the records written
+     integer(c_int) function c2d_census_write(ctx, path, n_written) bind(C, name='c2d_census_write')
+       import :: c_int, c_ptr, c_char, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int64_t), intent(out) :: n_written
+     end function c2d_census_write
+
+     ! the same for n caller-supplied records in the layout of c2d_census_export
+     integer(c_int) function c2d_census_write_from(ctx, d6, i5, keys, n, path) &
+          bind(C, name='c2d_census_write_from')
+       import :: c_int, c_ptr, c_char, c_double, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       real(c_double), intent(in) :: d6(6, *)
+       integer(c_int32_t), intent(in) :: i5(5, *)
+       integer(c_int64_t), intent(in) :: keys(*)
+       integer(c_int64_t), value :: n
+       character(kind=c_char), intent(in) :: path(*)
+     end function c2d_census_write_from
+
+     ! a census record file (read_cens) into the context's census, parsed
+     ! and converted on the device; n = the records of the file
+     integer(c_int) function c2d_census_read(ctx, path, n) bind(C, name='c2d_census_read')
+       import :: c_int, c_ptr, c_char, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int64_t), intent(out) :: n
+     end function c2d_census_read
+
+     ! parse only: the first min(cap, n) records to host arrays (c_loc of
+     ! them, or c_null_ptr with cap = 0 to count); the census is untouched
+     integer(c_int) function c2d_census_read_records(ctx, path, d6, i5, keys, cap, n) &
+          bind(C, name='c2d_census_read_records')
+       import :: c_int, c_ptr, c_char, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       type(c_ptr), value :: d6, i5, keys
+       integer(c_int64_t), value :: cap
+       integer(c_int64_t), intent(out) :: n
+     end function c2d_census_read_records
+
+     integer(c_int) function c2d_last_census_file_ms(ctx, io_ms, wait_ms, kernel_ms, convert_ms, &
+          device_records, host_records, chunks) bind(C, name='c2d_last_census_file_ms')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: io_ms, wait_ms, kernel_ms, convert_ms
+       integer(c_int64_t), intent(out) :: device_records, host_records
+       integer(c_int32_t), intent(out) :: chunks
+     end function c2d_last_census_file_ms
+
      integer(c_int) function c2d_fp_set_config(ctx, fcfg) bind(C, name='c2d_fp_set_config')
        import :: c_int, c_ptr, c2d_fp_config
        type(c_ptr), value :: ctx
