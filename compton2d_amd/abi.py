@@ -113,6 +113,21 @@ class FpIn(C.Structure):
                 ("nt", C.c_int32)]
 
 
+N_REF = 500          # C2D_NREF: energies of the Compton-reflection tables
+
+
+def reflect_tables_host():
+    """The Compton-reflection tables built on the host (c2d_reflect_tables_host;
+    no context, no GPU): E_ref [500] in keV, P_ref [n_in, n_out], W_abs [n_in, n_out]."""
+    from . import engine
+    lib = engine.load_library()
+    E, P, W = np.zeros(N_REF), np.zeros((N_REF, N_REF)), np.zeros((N_REF, N_REF))
+    rc = lib.c2d_reflect_tables_host(E.ctypes.data_as(PD), P.ctypes.data_as(PD), W.ctypes.data_as(PD))
+    if rc != 0:
+        raise engine.C2DError(rc, "c2d_reflect_tables_host: a P_ref column is not non-decreasing")
+    return E, P, W
+
+
 def tally_layout(nz: int, nr: int, nmu: int) -> dict:
     """Python restatement of c2d_tally_layout_for (include/compton2d.h)."""
     nc = nz * nr

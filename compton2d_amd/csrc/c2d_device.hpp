@@ -347,6 +347,14 @@ struct KParams {
    * (C2D_CDF_GUIDE + 1) + q] = the smallest i in [1, 400] with cdf(i) >= q / C2D_CDF_GUIDE
    * (400 if none), t 0: eps_tot, 1: eps_th; null: the full binary search */
   const uint16_t* cdf_guide;
+  /* Compton reflection (c2d_config.cr_sent, c2d_reflect.hpp; read by the
+   * reflecting kernel instances only): the tables [n_in][n_out] (null for
+   * cr_sent 0 and 4) and the step's Ed_ref[nr] + specular, matrix, disk counts */
+  int32_t cr_sent;
+  const double* refl_E;
+  const double* refl_P;
+  const double* refl_W;
+  double* refl_out;
 };
 #define C2D_CDF_GUIDE 256
 

@@ -40,6 +40,11 @@
  *                      counters c0 + 5j .. c0 + 5j + 4 of the packet's stream (c0:
  *                      the counter at the call), the rest of compb2d follows
  *                      c0 + 5 (j_accepted + 1)
+ *   Compton reflection (imcleak2d.f:124-149, :222-257; c2d_reflect.hpp): the next
+ *                      counters of the packet's own stream (key, sub, ctr) in the
+ *                      reference's order -- rnum, the xnu draw only if n_out > 1, the
+ *                      disk's wmu -- and ctr advances by the draws taken; probe copies
+ *                      never reflect, the recombined copy draws from (K_src, C2D_SUB_RECOMB)
  * Draw n of (key, sub) = u53(mix64(key + gamma * ((sub << 32 | n) + 1)));
  * derive(key, tag, a, b; sub) = Philox_key({a, b, tag | sub << 8, C_DERIVE}).
  */

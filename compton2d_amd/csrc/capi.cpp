@@ -22,6 +22,7 @@
 #include "c2d_rng.h"
 #include "pspt_host.h"
 #include "plcm_host.h"
+#include "reflect_host.h"
 #include "c2d_censfmt.h"
 #include "c2d_censtext.hpp"
 #include "c2d_evparse.hpp"
@@ -30,23 +31,23 @@
 using namespace c2d;
 
 extern "C" int c2d_launch_transport_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
-                                          int trk, hipStream_t s);
+                                          int trk, int refl, hipStream_t s);
 extern "C" int c2d_launch_transport_fast(const KParams* P, const GenArgs* A, int grid, size_t lds,
-                                         int trk, hipStream_t s);
+                                         int trk, int refl, hipStream_t s);
 extern "C" int c2d_launch_source_exact(const KParams* P, int grid, hipStream_t s);
 extern "C" int c2d_launch_source_fast(const KParams* P, int grid, hipStream_t s);
 extern "C" int c2d_launch_scatter_exact(const KParams* P, const GenArgs* A, int grid, int hard_grid, hipStream_t s);
 extern "C" int c2d_launch_scatter_fast(const KParams* P, const GenArgs* A, int grid, int hard_grid, hipStream_t s);
-extern "C" int c2d_transport_occupancy_exact(int* blocks_per_cu, size_t lds, int trk);
-extern "C" int c2d_transport_occupancy_fast(int* blocks_per_cu, size_t lds, int trk);
+extern "C" int c2d_transport_occupancy_exact(int* blocks_per_cu, size_t lds, int trk, int refl);
+extern "C" int c2d_transport_occupancy_fast(int* blocks_per_cu, size_t lds, int trk, int refl);
 extern "C" int c2d_aux_occupancy_exact(int which, int* blocks_per_cu);
 extern "C" int c2d_aux_occupancy_fast(int which, int* blocks_per_cu);
 extern "C" int c2d_launch_bundle_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
-                                       int trk, int evq, hipStream_t s);
+                                       int trk, int evq, int refl, hipStream_t s);
 extern "C" int c2d_launch_bundle_fast(const KParams* P, const GenArgs* A, int grid, size_t lds,
-                                      int trk, int evq, hipStream_t s);
-extern "C" int c2d_bundle_occupancy_exact(int* blocks_per_cu, size_t lds, int trk, int evq);
-extern "C" int c2d_bundle_occupancy_fast(int* blocks_per_cu, size_t lds, int trk, int evq);
+                                      int trk, int evq, int refl, hipStream_t s);
+extern "C" int c2d_bundle_occupancy_exact(int* blocks_per_cu, size_t lds, int trk, int evq, int refl);
+extern "C" int c2d_bundle_occupancy_fast(int* blocks_per_cu, size_t lds, int trk, int evq, int refl);
 extern "C" int c2d_launch_comtab_sigma(const double* gnt, double* S, hipStream_t s);
 extern "C" int c2d_launch_comtab_gemm(const double* f_nt, const double* gnt, const double* S,
                                       double* tab, int ncell, hipStream_t s);
@@ -229,6 +230,13 @@ struct c2d_ctx {
   bool have_electrons = false;  /* f_nt/Pnt hold an electron state (C2D_DEV_ELECTRONS) */
   bool have_vem = false;        /* vem_* hold the last c2d_volume_em tables (C2D_DEV_EMISSION) */
   int32_t* mono_flag = nullptr;
+  /* Compton reflection (cfg.cr_sent != 0): the tables on the device (cr_sent
+   * 1..3; E_ref | P_ref | W_abs in one allocation), the step's Ed_ref[nr] +
+   * three counts, and a buffer of the same size for the world sum */
+  double* refl_tab = nullptr;
+  double* refl_out = nullptr;
+  double* refl_red = nullptr;
+  bool refl_stepped = false;     /* a step has run: c2d_reflect_result has something to return */
   /* RCCL communicator of the tally all-reduce (c2d_comm_init) */
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_world = 1;
@@ -356,7 +364,7 @@ extern "C" int c2d_init(const c2d_config* cfg, c2d_ctx** out) {
   if (cfg->nphtotal < 1 || cfg->nphtotal > C2D_NPHOMAX || cfg->nph_lc < 0 ||
       cfg->nph_lc > C2D_NPHLCMAX || cfg->nmu < 1 || cfg->nmu > C2D_NMUMAX)
     return C2D_E_ARG;
-  if (cfg->cr_sent != 0) return C2D_E_ARG;   /* Compton reflection not supported */
+  if (cfg->cr_sent < 0 || cfg->cr_sent > 4) return C2D_E_ARG;   /* include/compton2d.h: 0..4 */
   if (cfg->trk_variant != C2D_TRK_SRC && cfg->trk_variant != C2D_TRK_2012_11) return C2D_E_ARG;
   if (cfg->split1 < 1 || cfg->split2 < 1 || cfg->split3 < 1 || cfg->world < 1 ||
       cfg->rank < 0 || cfg->rank >= cfg->world)
@@ -429,6 +437,20 @@ extern "C" int c2d_init(const c2d_config* cfg, c2d_ctx** out) {
   HIPCHK(c, dalloc(&c->surf_tbb, (size_t)c->nslot));
   HIPCHK(c, dalloc(&c->surf_spec, (size_t)c->nslot));
   HIPCHK(c, dalloc(&c->tbbl, (size_t)c->nr));
+  if (cfg->cr_sent != 0) {
+    HIPCHK(c, dalloc(&c->refl_out, (size_t)c->nr + 3));
+    HIPCHK(c, dalloc(&c->refl_red, (size_t)c->nr + 3));
+    HIPCHK(c, hipMemset(c->refl_out, 0, sizeof(double) * (c->nr + 3)));
+  }
+  if (cfg->cr_sent >= 1 && cfg->cr_sent <= 3) {
+    const size_t N = C2D_NREF;
+    std::vector<double> tab(N + 2 * N * N);
+    const int bad = c2d_reflect_build(tab.data(), tab.data() + N, tab.data() + N + N * N);
+    if (bad)
+      return fail(c, C2D_E_ARG, "reflection matrix: P_ref column n_in = %d is not non-decreasing in n_out", bad);
+    HIPCHK(c, dalloc(&c->refl_tab, tab.size()));
+    HIPCHK(c, hipMemcpy(c->refl_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+  }
   if (cfg->comtot_mode == C2D_COMTOT_TABLE) {
     HIPCHK(c, dalloc(&c->comtab, nc * C2D_COMTAB_N));
     HIPCHK(c, dalloc(&c->comS, (size_t)C2D_COMTAB_N * C2D_NUM_NT));
@@ -457,15 +479,15 @@ extern "C" int c2d_init(const c2d_config* cfg, c2d_ctx** out) {
    * from the runtime's occupancy calculator for this kernel and LDS size) */
   int blocks_per_cu = 0;
   int orc = cfg->comtot_mode == C2D_COMTOT_TABLE
-                ? c2d_transport_occupancy_fast(&blocks_per_cu, c->lds_bytes, cfg->trk_variant)
-                : c2d_transport_occupancy_exact(&blocks_per_cu, c->lds_bytes, cfg->trk_variant);
+                ? c2d_transport_occupancy_fast(&blocks_per_cu, c->lds_bytes, cfg->trk_variant, cfg->cr_sent != 0)
+                : c2d_transport_occupancy_exact(&blocks_per_cu, c->lds_bytes, cfg->trk_variant, cfg->cr_sent != 0);
   if (orc) return fail(c, C2D_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)orc));
   c->max_grid = c->n_cu * std::max(1, blocks_per_cu);
   {
     auto occ = cfg->comtot_mode == C2D_COMTOT_TABLE ? c2d_bundle_occupancy_fast
                                                     : c2d_bundle_occupancy_exact;
     int b0 = 0;
-    orc = occ(&b0, c->lds_bytes, cfg->trk_variant, 0);
+    orc = occ(&b0, c->lds_bytes, cfg->trk_variant, 0, cfg->cr_sent != 0);
     if (orc) return fail(c, C2D_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)orc));
     c->bundle_lds = c->lds_bytes;
     c->bundle_grid = c->n_cu * std::max(1, b0);
@@ -480,9 +502,12 @@ extern "C" int c2d_init(const c2d_config* cfg, c2d_ctx** out) {
       cap = (int)std::max<long long>(0, std::min<long long>(C2D_EVQ_MAX, atoll(e)));
       need = 1;
     }
+    /* a reflecting deck keeps the inline path: a reflection draws from the
+     * packet's stream, and a queue entry carries no stream position */
+    if (cfg->cr_sent != 0) cap = 0;
     if (cap > 0 && b0 > 0) {
       int b1 = 0;
-      orc = occ(&b1, c->lds_bytes + evq_lds, cfg->trk_variant, 1);
+      orc = occ(&b1, c->lds_bytes + evq_lds, cfg->trk_variant, 1, 0);
       if (orc) return fail(c, C2D_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)orc));
       if (b1 >= need) {
         c->evq_cap = cap;
@@ -579,6 +604,9 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
     if (c->cens[b].tg) (void)hipFree(c->cens[b].tg);
   }
   for (double* p : c->spec_bufs) (void)hipFree(p);
+  void* rptrs[] = {c->refl_tab, c->refl_out, c->refl_red};
+  for (void* p : rptrs)
+    if (p) (void)hipFree(p);
   void* optrs[] = {c->obs_edges, c->obs_hist, c->obs_ev, c->pspt_red, c->cdf_guide, c->oset_edges};
   for (void* p : optrs)
     if (p) (void)hipFree(p);
@@ -1448,6 +1476,11 @@ static int run_step_body(c2d_ctx* c) {
   P.err = c->derr;
   P.lds_cells = c->lds_cells;
   P.evq_cap = c->evq_cap;
+  P.cr_sent = cfg.cr_sent;
+  P.refl_E = c->refl_tab;
+  P.refl_P = c->refl_tab ? c->refl_tab + C2D_NREF : nullptr;
+  P.refl_W = c->refl_tab ? c->refl_tab + C2D_NREF + (size_t)C2D_NREF * C2D_NREF : nullptr;
+  P.refl_out = c->refl_out;
   P.prof = c->ctl + CTL_PROF;
   P.n_vol_global = c->n_vol_global;
   P.n_surf_global = c->n_surf_global;
@@ -1506,6 +1539,7 @@ static int run_step_body(c2d_ctx* c) {
     if (rc) return rc;
   }
   HIPCHK(c, hipMemsetAsync(c->derr, 0, sizeof(int32_t), c->stream));
+  if (c->refl_out) HIPCHK(c, hipMemsetAsync(c->refl_out, 0, sizeof(double) * (c->nr + 3), c->stream));
 
   const bool fast = cfg.comtot_mode == C2D_COMTOT_TABLE;
   auto launch_tr = fast ? c2d_launch_transport_fast : c2d_launch_transport_exact;
@@ -1551,7 +1585,7 @@ static int run_step_body(c2d_ctx* c) {
       const int grid = (int)std::max<int64_t>(
           1, std::min<int64_t>(gmax, (A.n_items + C2D_TR_BLOCK - 1) / C2D_TR_BLOCK));
       c->g0_launched = true;
-      int rc = launch_b(c->dP, &A, grid, c->bundle_lds, cfg.trk_variant, c->evq_cap > 0, c->stream);
+      int rc = launch_b(c->dP, &A, grid, c->bundle_lds, cfg.trk_variant, c->evq_cap > 0, cfg.cr_sent != 0, c->stream);
       if (rc) return fail(c, C2D_E_HIP, "bundle launch (gen 0): %s", hipGetErrorString((hipError_t)rc));
       launches++;
     }
@@ -1601,7 +1635,7 @@ static int run_step_body(c2d_ctx* c) {
       A.kn_cap = kn_cap; A.sc_k1 = sc_k1;
       int rc = launch_sc(c->dP, &A, aux_grid(e - b, c->sc_grid), 2 * c->n_cu, c->stream);
       if (rc) return fail(c, C2D_E_HIP, "scatter launch (gen %d): %s", gen, hipGetErrorString((hipError_t)rc));
-      rc = launch_tr(c->dP, &A, tr_grid(e - b), c->lds_bytes, cfg.trk_variant, c->stream);
+      rc = launch_tr(c->dP, &A, tr_grid(e - b), c->lds_bytes, cfg.trk_variant, cfg.cr_sent != 0, c->stream);
       if (rc) return fail(c, C2D_E_HIP, "transport launch (gen %d): %s", gen, hipGetErrorString((hipError_t)rc));
       launches += 2;
     }
@@ -1704,6 +1738,7 @@ static int run_step_body(c2d_ctx* c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->n_ev = 0;
   c->ev_stepped = true;
+  c->refl_stepped = true;
   unsigned long long ev_reserved = 0;
   for (int sh = 0; sh < C2D_EV_SHARDS; sh++) {
     const unsigned long long m = ctl[CTL_EVSH + sh * C2D_EV_SHARD_STRIDE];
@@ -1728,6 +1763,49 @@ static int run_step_body(c2d_ctx* c) {
   if (herr & ERR_SPEC) return fail(c, C2D_E_ARG, "surface packet without a seed spectrum");
   if (herr & ERR_NONFINITE)
     return fail(c, C2D_E_NONFINITE, "NaN/Inf in the step's tallies (edep, n_field, ecens, ...)");
+  return C2D_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Compton reflection: tables and per-step results                     */
+/* ------------------------------------------------------------------ */
+extern "C" int c2d_reflect_tables_host(double* E_ref, double* P_ref, double* W_abs) {
+  return c2d_reflect_build(E_ref, P_ref, W_abs) ? C2D_E_ARG : C2D_OK;
+}
+
+extern "C" int c2d_reflect_tables(c2d_ctx* c, double* E_ref, double* P_ref, double* W_abs) {
+  if (!c) return C2D_E_ARG;
+  if (!c->refl_tab)
+    return fail(c, C2D_E_STATE, "c2d_reflect_tables: cr_sent = %d uses no tables", (int)c->cfg.cr_sent);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t N = C2D_NREF;
+  if (E_ref) HIPCHK(c, hipMemcpy(E_ref, c->refl_tab, sizeof(double) * N, hipMemcpyDeviceToHost));
+  if (P_ref) HIPCHK(c, hipMemcpy(P_ref, c->refl_tab + N, sizeof(double) * N * N, hipMemcpyDeviceToHost));
+  if (W_abs) HIPCHK(c, hipMemcpy(W_abs, c->refl_tab + N + N * N, sizeof(double) * N * N, hipMemcpyDeviceToHost));
+  return C2D_OK;
+}
+
+extern "C" int c2d_reflect_result(c2d_ctx* c, double* Ed_ref, int64_t counts[3], int32_t world_sum) {
+  if (!c) return C2D_E_ARG;
+  if (!c->refl_stepped) return fail(c, C2D_E_STATE, "c2d_reflect_result: no step has run yet");
+  const size_t n = (size_t)c->nr + 3;
+  std::vector<double> h(n, 0.0);
+  if (c->refl_out) {
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const double* src = c->refl_out;
+    if (world_sum) {
+      if (!c->comm) return fail(c, C2D_E_STATE, "c2d_reflect_result: world_sum needs c2d_comm_init");
+      const ncclResult_t r = ncclAllReduce(c->refl_out, c->refl_red, n, ncclDouble, ncclSum, c->comm, c->stream);
+      if (r != ncclSuccess) return fail(c, C2D_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
+      src = c->refl_red;
+    }
+    HIPCHK(c, hipMemcpyAsync(h.data(), src, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (Ed_ref)
+    for (int k = 0; k < c->nr; k++) Ed_ref[k] = h[k];
+  if (counts)
+    for (int i = 0; i < 3; i++) counts[i] = (int64_t)h[c->nr + i];
   return C2D_OK;
 }
 

@@ -235,3 +235,86 @@ extern "C" int c2d_selftest_mcd_fast(int device, const double* z_host, int n, do
   if (out) (void)hipFree(out);
   return rc;
 }
+
+/* The reflection functions of the transport kernels (c2d_reflect.hpp) on n
+ * packet states, one thread each: boundary 0 = the lower boundary (ring 1),
+ * 1 = the outer r-boundary; time = C2D_ST_REFL_TIME, dt = C2D_ST_REFL_DT;
+ * stream (keys[i], sub 0) from counter 0.  in[8n] = xnu, ew, wmu, rpre, zpre,
+ * phi, dcen, tbbl; out[10n] = xnu, ew, wmu, rpre, zpre, t_bound, draws taken,
+ * idead, n_in, n_out (0: no matrix lookup).  t_bound is imcleak's
+ * time + dt - rad_cp dcen unless the disk reflected.  The Ed_ref adds go
+ * through the same atomics into a one-ring scratch array whose sum is
+ * returned.  spec_switch only decides a tally (fout) that this entry does not
+ * hold: it is checked and otherwise unused. */
+#include "c2d_reflect.hpp"
+#include "reflect_host.h"
+
+#define C2D_ST_REFL_TIME 100.0
+#define C2D_ST_REFL_DT 10.0
+
+namespace c2d {
+__global__ void __launch_bounds__(256) c2d_selftest_reflect_kernel(ReflTab R, int boundary, int cr_sent,
+                                                                   const double* in, const uint64_t* keys,
+                                                                   int64_t n, double* out) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* s = in + 8 * i;
+  ReflPkt q;
+  q.xnu = s[0]; q.ew = s[1]; q.wmu = s[2]; q.rpre = s[3]; q.zpre = s[4]; q.dcen = s[6];
+  q.key = keys[i]; q.sub = 0u; q.ctr = 0u; q.n_in = 0; q.n_out = 0;
+  double tb = C2D_ST_REFL_TIME + C2D_ST_REFL_DT - REFL_RAD_CP * q.dcen;
+  int idead = 1;
+  if (boundary == 0) {
+    if (reflect_lower(R, cr_sent, s[7], 1, q) != REFL_NONE) idead = 0;
+  } else {
+    (void)reflect_outer(R, cr_sent, C2D_ST_REFL_TIME, C2D_ST_REFL_DT, q, tb);
+  }
+  double* o = out + 10 * i;
+  o[0] = q.xnu; o[1] = q.ew; o[2] = q.wmu; o[3] = q.rpre; o[4] = q.zpre; o[5] = tb;
+  o[6] = (double)q.ctr; o[7] = (double)idead; o[8] = (double)q.n_in; o[9] = (double)q.n_out;
+}
+}  // namespace c2d
+
+extern "C" int c2d_selftest_reflect(int device, int boundary, int cr_sent, int spec_switch, const double* in_host,
+                                    const uint64_t* keys_host, int64_t n, double* out_host, double* Ed_ref_sum) {
+  if (boundary < 0 || boundary > 1 || cr_sent < 0 || cr_sent > 4 || spec_switch < 0 || spec_switch > 1) return -1;
+  if (Ed_ref_sum) *Ed_ref_sum = 0.0;
+  if (n <= 0) return 0;
+  if (hipSetDevice(device) != hipSuccess) return -2;
+  const size_t N = C2D_NREF;
+  std::vector<double> tab(N + 2 * N * N);
+  if (c2d_reflect_build(tab.data(), tab.data() + N, tab.data() + N + N * N)) return -1;
+  double *dtab = nullptr, *in = nullptr, *out = nullptr, *res = nullptr;
+  uint64_t* keys = nullptr;
+  int rc = 0;
+  if (hipMalloc((void**)&dtab, tab.size() * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&in, 8 * (size_t)n * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&out, 10 * (size_t)n * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&keys, (size_t)n * sizeof(uint64_t)) != hipSuccess ||
+      hipMalloc((void**)&res, 4 * sizeof(double)) != hipSuccess)
+    rc = -2;
+  if (!rc && (hipMemcpy(dtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(in, in_host, 8 * (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(keys, keys_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemset(res, 0, 4 * sizeof(double)) != hipSuccess))
+    rc = -2;
+  if (!rc) {
+    c2d::ReflTab R;
+    R.E = dtab; R.P = dtab + N; R.W = dtab + N + N * N; R.out = res; R.nr = 1;
+    hipLaunchKernelGGL(c2d::c2d_selftest_reflect_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, R,
+                       boundary, cr_sent, in, keys, n, out);
+    if (hipDeviceSynchronize() != hipSuccess) rc = -2;
+  }
+  double h[4] = {0, 0, 0, 0};
+  if (!rc && (hipMemcpy(out_host, out, 10 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(h, res, sizeof h, hipMemcpyDeviceToHost) != hipSuccess))
+    rc = -2;
+  if (!rc && Ed_ref_sum) *Ed_ref_sum = h[0];
+  if (dtab) (void)hipFree(dtab);
+  if (in) (void)hipFree(in);
+  if (out) (void)hipFree(out);
+  if (keys) (void)hipFree(keys);
+  if (res) (void)hipFree(res);
+  return rc;
+}

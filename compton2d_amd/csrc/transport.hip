@@ -69,6 +69,7 @@ __device__ __forceinline__ double c2d_mdiv_rcp(double a, double b) {
 #include "c2d_device.hpp"
 #include "c2d_math.h"
 #include "c2d_rng.h"
+#include "c2d_reflect.hpp"
 
 #ifndef C2D_VARIANT
 #define C2D_VARIANT 0
@@ -876,7 +877,7 @@ __device__ __forceinline__ int compb2d_w(const KParams& P, const Geo* g, double*
 }
 
 /* ------------------------------------------------------------------ */
-/* escapes (src/imcleak2d.f:2-320, cr_sent = 0)                          */
+/* escapes (src/imcleak2d.f:2-320; REFL: the cr_sent != 0 branches)      */
 /* ------------------------------------------------------------------ */
 __device__ __forceinline__ void push_event(const KParams& P0, double tb, const Pkt& p, LaneCnt& lc) {
   const KParams& P = cold(P0);
@@ -905,7 +906,51 @@ __device__ __forceinline__ void escape_tally(const KParams& P0, const Tal& T, co
     atomicAdd(&T_FOUT(P, T)[(jgpmu - 1) * C2D_NPHOMAX + (jgpsp - 1)], p.ew);
 }
 
-/* returns idead: 1 = left the system, 0 = continue (axis pass-through) */
+/* Compton reflection (c2d_reflect.hpp) on a tracked packet: the reflection
+ * itself, then get_bin (imcleak2d.f:161, :261).  refl_lower: true when the
+ * packet was reflected back into zone row 1 (no escape, no event). */
+__device__ __forceinline__ ReflTab refl_tab(const KParams& P) {
+  ReflTab R;
+  R.E = P.refl_E; R.P = P.refl_P; R.W = P.refl_W; R.out = P.refl_out; R.nr = P.nr;
+  return R;
+}
+__device__ __forceinline__ ReflPkt refl_pkt(const Pkt& p) {
+  ReflPkt q;
+  q.xnu = p.xnu; q.ew = p.ew; q.wmu = p.wmu; q.rpre = p.rpre; q.zpre = p.zpre; q.dcen = p.dcen;
+  q.key = p.key; q.sub = p.sub; q.ctr = p.ctr; q.n_in = 0; q.n_out = 0;
+  return q;
+}
+__device__ __forceinline__ void refl_store(const KParams& P, const Tal& T, Pkt& p, const ReflPkt& q) {
+  p.xnu = q.xnu; p.ew = q.ew; p.wmu = q.wmu; p.rpre = q.rpre; p.zpre = q.zpre; p.ctr = q.ctr;
+  set_bins(p, bin_sp(T.g, P.nphtotal, p.xnu, F32(1.000001), F32(0.999999), 0), bin_lc(T.g, P.nph_lc, p.xnu),
+           bin_mu(T.g, P.nmu, p.wmu));
+}
+__device__ __forceinline__ bool refl_lower(const KParams& P, const Tal& T, Pkt& p) {
+  const double tbbl = gld(P.tbbl + (p.kph - 1));
+  ReflPkt q = refl_pkt(p);
+  const ReflTab R = refl_tab(P);
+  const int kind = reflect_lower(R, P.cr_sent, tbbl, p.kph, q);
+  if (kind == REFL_NONE) return false;
+  if (tbbl > 0.0) {                       /* imcleak2d.f:95-102, before the reflection */
+    gadd(&P.T[P.off.Ed_in + p.kph - 1], p.ew);
+    atomicAdd(&T_ERLKL(P, T)[p.kph - 1], p.ew);
+  }
+  if (kind == REFL_SPECULAR && P.spec_switch == 1 && JGPSP(p) > 0)   /* the bins from before (:116) */
+    atomicAdd(&T_FOUT(P, T)[(JGPMU(p) - 1) * C2D_NPHOMAX + (JGPSP(p) - 1)], p.ew);
+  refl_store(P, T, p, q);
+  p.jph = 1;
+  return true;
+}
+__device__ __forceinline__ void refl_outer(const KParams& P, const Tal& T, Pkt& p, double& tb) {
+  ReflPkt q = refl_pkt(p);
+  const ReflTab R = refl_tab(P);
+  if (reflect_outer(R, P.cr_sent, P.time, P.dt, q, tb) != REFL_NONE) refl_store(P, T, p, q);
+}
+
+/* returns idead: 1 = left the system, 0 = continue (axis pass-through; REFL:
+ * reflected at the lower boundary, jph = 1).  REFL 0 is the cr_sent = 0 code;
+ * REFL 1 (cr_sent 1..4) adds the reflecting branches. */
+template <int REFL = 0>
 C2D_COLD_FN int imcleak(const KParams& P0, const Tal& T, Pkt& p, LaneCnt& lc) {
   const KParams& P = cold(P0);
   if (p.kph == 0) {
@@ -918,6 +963,7 @@ C2D_COLD_FN int imcleak(const KParams& P0, const Tal& T, Pkt& p, LaneCnt& lc) {
     p.kph = 1;
     return 0;
   }
+  if (REFL && p.jph <= 0 && refl_lower(P, T, p)) return 0;   /* no escape, no event */
   LC_ADD(lc, C2D_CNT_ESCAPES);
   const double tb = P.time + P.dt - RAD_CP * p.dcen;   /* H4: fresh t_bound everywhere */
   if (p.jph <= 0) {
@@ -933,6 +979,17 @@ C2D_COLD_FN int imcleak(const KParams& P0, const Tal& T, Pkt& p, LaneCnt& lc) {
   }
   if (p.jph != P.nz + 1) {
     atomicAdd(&T_ERLKO(P, T)[p.jph - 1], p.ew);
+    if (REFL) {
+      /* the disk (cr_sent 2, 3; wmu <= 0): new xnu, ew, wmu, bins and the
+       * reference's own t_bound; every other packet leaves as it is */
+      double tbo = tb;
+      refl_outer(P, T, p, tbo);
+      if (P.ncycle > 0) {
+        push_event(P, tbo, p, lc);
+        escape_tally(P, T, p);
+      }
+      return 1;
+    }
     if (P.ncycle > 0) {
       push_event(P, tb, p, lc);
       escape_tally(P, T, p);
@@ -1375,7 +1432,7 @@ struct Prof {
  * C2D_TRK_2012_11; include/compton2d.h): the azimuth update with the path's
  * r-plane projection f, colmfp kept across cell boundaries, clamps at 1.
  * V12 = 0 is src/imctrk2d.f bug for bug (hazard H1). */
-template <int V12>
+template <int V12, int REFL = 0>
 __device__ __forceinline__ int flight(const KParams& P, const Tal& T, Pkt& p, ComCache& cc, LaneCnt& lc,
                                       Prof& pf) {
   const double lim8 = V12 ? 1.0 : 9.9999999e-1, lim9 = V12 ? 1.0 : 0.999999999;
@@ -1561,11 +1618,15 @@ __device__ __forceinline__ int flight(const KParams& P, const Tal& T, Pkt& p, Co
       p.kph = knew;
       if (p.mode == -1) return FL_END;
       TP_COUNT(pf, TP_LEAK_W, TP_LEAK_L);
-      if (imcleak(P, T, p, lc) == 1) {
+      if (imcleak<REFL>(P, T, p, lc) == 1) {
         if (p.mode == 1) LC_ADD(lc, C2D_CNT_ESC_SCAT);
         return FL_END;
       }
       set_phi(p, p.phi);                        /* axis pass-through set phi = 1e-6 */
+      if (REFL) {                               /* a reflection changed xnu: its caches */
+        cache_energy(P, g, p);
+        cc.cell0 = -1; cc.cell1 = -1;
+      }
       return FL_CONT;
     }
     p.kph = knew;
@@ -2283,7 +2344,9 @@ __device__ __forceinline__ void load_source(const KParams& P0, Pkt& p, long long
 /* Every secondary is an imctrk2d(1) track (imctrk2d.f:662-679) from the
  * packet store; generation 0 (census + sources, the split1 probes and the
  * recombined copy) runs as probe bundles (c2d_bundle_kernel below). */
-template <int V12>
+/* REFL 1: imcleak's reflecting branches (cr_sent 1..4); REFL 0 is the
+ * cr_sent = 0 kernel as it was (the same instructions) */
+template <int V12, int REFL = 0>
 __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_transport_kernel)(const KParams* __restrict__ Pg,
                                                                       const GenArgs A) {
   const KParams& P = *Pg;
@@ -2370,7 +2433,7 @@ __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_transport_kerne
 #ifdef C2D_TR_PROF
       pf.acc[TP_LANES] += __popcll(__ballot(1));
 #endif
-      const int out = flight<V12>(P, T, p, cc, lc, pf);
+      const int out = flight<V12, REFL>(P, T, p, cc, lc, pf);
       TP_MARK(pf, TP_EVENT);
       if (out != FL_CONT) {
         if (out == FL_COLLIDE) push_scat(P, A.q2_out, A.n2_out, make_rec(p, p.key, p.ctr));
@@ -2572,7 +2635,7 @@ __device__ __forceinline__ void probe_collide(const KParams& P, const Tal& T, co
 }
 
 /* one shared step of the bundle (flight() for every copy on the path) */
-template <int V12, int EVQ>
+template <int V12, int EVQ, int REFL = 0>
 __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, const GenArgs& A,
                                             Bundle& b, ComCache& cc, LaneCnt& lc, Prof& pf,
                                             CensRec& nr, long long nitem, int& nst) {
@@ -2790,8 +2853,16 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
         if (b.flags & BF_TRACK) {
           TP_COUNT(pf, TP_LEAK_W, TP_LEAK_L);
           if (!EVQ) {
-            if (imcleak(P, T, p, lc) == 1) b.flags &= ~BF_TRACK;
-            else set_phi(p, p.phi);             /* axis pass-through set phi = 1e-6 */
+            if (imcleak<REFL>(P, T, p, lc) == 1) {
+              b.flags &= ~BF_TRACK;
+            } else {
+              set_phi(p, p.phi);                /* axis pass-through set phi = 1e-6 */
+              if (REFL) {                       /* a reflection changed xnu: its caches (the probes
+                                                   have ended, so the bundle's comtot is not read) */
+                cache_energy(P, g, p);
+                cc.cell0 = -1; cc.cell1 = -1;
+              }
+            }
           } else if (p.kph == 0 && !(P.rmin > 1.0e-10)) {
             p.kph = 1;                          /* imcleak's axis pass-through */
             set_phi(p, 1.0e-6);
@@ -2954,9 +3025,8 @@ __device__ __forceinline__ void bundle_step(const KParams& P1, const Tal& T, con
 
 /* EVQ 1: escapes through the waves' queues (KParams.evq_cap >= 1), 0: inline
  * (both paths in one kernel cost 2 VGPRs over the 168 of 3 waves per SIMD) */
-template <int V12, int EVQ>
-__global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(const KParams* __restrict__ Pg,
-                                                                   const GenArgs A) {
+template <int V12, int EVQ, int REFL>
+__device__ __forceinline__ void bundle_body(const KParams* __restrict__ Pg, const GenArgs& A) {
   const KParams& P = *Pg;
   double* const lds = c2d_tr_lds;
   const int tid = threadIdx.x;
@@ -3104,7 +3174,7 @@ __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(
 #ifdef C2D_TR_PROF
       pf.acc[TP_LANES] += __popcll(__ballot(1));
 #endif
-      bundle_step<V12, EVQ>(P, T, A, b, cc, lc, pf, nr, nitem, nst);
+      bundle_step<V12, EVQ, REFL>(P, T, A, b, cc, lc, pf, nr, nitem, nst);
       TP_MARK(pf, TP_EVENT);
     }
     if (EVQ) {
@@ -3189,6 +3259,19 @@ __global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(
   flush_counters(P, lc, lane);
 }
 
+template <int V12, int EVQ>
+__global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_kernel)(const KParams* __restrict__ Pg,
+                                                                   const GenArgs A) {
+  bundle_body<V12, EVQ, 0>(Pg, A);
+}
+/* cr_sent 1..4: the inline escape path with imcleak<1> (queue entries carry
+ * no RNG position, so the reflecting instance has no escape queue) */
+template <int V12>
+__global__ void __launch_bounds__(BLOCK) C2D_TR_ATTR C2D_SFX(c2d_bundle_refl_kernel)(const KParams* __restrict__ Pg,
+                                                                        const GenArgs A) {
+  bundle_body<V12, 0, 1>(Pg, A);
+}
+
 #if C2D_TABLE_COMTOT
 /* Per-step comtot table: tab[cell][g] = sum_i sigma_E(i, x_g) f_nt(cell,i) dg_i
  * (src/comtot2d.f:220-241 without the n_e factor).  sigma_E(i, x_g) does not
@@ -3252,18 +3335,26 @@ __global__ void __launch_bounds__(256) c2d_comtab_gemm(const double* f_nt, const
 /* launchers (called from capi.cpp)                                    */
 /* ------------------------------------------------------------------ */
 /* trk: c2d_config.trk_variant (0: src/imctrk2d.f, 1: src_20121113) */
+/* refl: the reflecting instance (c2d_config.cr_sent != 0) */
 extern "C" int C2D_SFX(c2d_launch_transport)(const c2d::KParams* P_dev, const c2d::GenArgs* A, int grid,
-                                             size_t lds_bytes, int trk, hipStream_t stream) {
-  if (trk)
-    hipLaunchKernelGGL(C2D_SFX(c2d::c2d_transport_kernel)<1>, dim3(grid), dim3(c2d::BLOCK), lds_bytes,
+                                             size_t lds_bytes, int trk, int refl, hipStream_t stream) {
+  if (refl && trk)
+    hipLaunchKernelGGL((C2D_SFX(c2d::c2d_transport_kernel)<1, 1>), dim3(grid), dim3(c2d::BLOCK), lds_bytes,
+                       stream, P_dev, *A);
+  else if (refl)
+    hipLaunchKernelGGL((C2D_SFX(c2d::c2d_transport_kernel)<0, 1>), dim3(grid), dim3(c2d::BLOCK), lds_bytes,
+                       stream, P_dev, *A);
+  else if (trk)
+    hipLaunchKernelGGL((C2D_SFX(c2d::c2d_transport_kernel)<1, 0>), dim3(grid), dim3(c2d::BLOCK), lds_bytes,
                        stream, P_dev, *A);
   else
-    hipLaunchKernelGGL(C2D_SFX(c2d::c2d_transport_kernel)<0>, dim3(grid), dim3(c2d::BLOCK), lds_bytes,
+    hipLaunchKernelGGL((C2D_SFX(c2d::c2d_transport_kernel)<0, 0>), dim3(grid), dim3(c2d::BLOCK), lds_bytes,
                        stream, P_dev, *A);
   return (int)hipGetLastError();
 }
 
-static const void* C2D_SFX(bundle_fn)(int trk, int evq) {
+static const void* C2D_SFX(bundle_fn)(int trk, int evq, int refl = 0) {
+  if (refl) return trk ? (const void*)C2D_SFX(c2d::c2d_bundle_refl_kernel)<1> : (const void*)C2D_SFX(c2d::c2d_bundle_refl_kernel)<0>;
   if (trk) return evq ? (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<1, 1> : (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<1, 0>;
   return evq ? (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<0, 1> : (const void*)C2D_SFX(c2d::c2d_bundle_kernel)<0, 0>;
 }
@@ -3274,23 +3365,28 @@ static int C2D_SFX(bundle_lds_attr)(size_t lds_bytes) {
     if (hipError_t e = hipFuncSetAttribute(C2D_SFX(bundle_fn)(v >> 1, v & 1),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes))
       return (int)e;
+  for (int v = 0; v < 2; v++)
+    if (hipError_t e = hipFuncSetAttribute(C2D_SFX(bundle_fn)(v, 0, 1),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes))
+      return (int)e;
   return 0;
 }
 
-/* evq: KParams.evq_cap > 0 (the escape-queue instance; lds_bytes includes the queues) */
+/* evq: KParams.evq_cap > 0 (the escape-queue instance; lds_bytes includes the queues);
+ * refl: the reflecting instance (cr_sent != 0; evq must be 0) */
 extern "C" int C2D_SFX(c2d_launch_bundle)(const c2d::KParams* P_dev, const c2d::GenArgs* A, int grid,
-                                          size_t lds_bytes, int trk, int evq, hipStream_t stream) {
+                                          size_t lds_bytes, int trk, int evq, int refl, hipStream_t stream) {
   if (int e = C2D_SFX(bundle_lds_attr)(lds_bytes)) return e;
   void* args[] = {(void*)&P_dev, (void*)A};
-  return (int)hipLaunchKernel(C2D_SFX(bundle_fn)(trk, evq), dim3(grid), dim3(c2d::BLOCK), args, lds_bytes,
+  return (int)hipLaunchKernel(C2D_SFX(bundle_fn)(trk, evq, refl), dim3(grid), dim3(c2d::BLOCK), args, lds_bytes,
                               stream);
 }
 
 /* trk: the tracker instance the context launches (c2d_config.trk_variant):
  * the occupancy is that instance's */
-extern "C" int C2D_SFX(c2d_bundle_occupancy)(int* blocks_per_cu, size_t lds_bytes, int trk, int evq) {
+extern "C" int C2D_SFX(c2d_bundle_occupancy)(int* blocks_per_cu, size_t lds_bytes, int trk, int evq, int refl) {
   if (C2D_SFX(bundle_lds_attr)(lds_bytes) != 0) { *blocks_per_cu = 0; return 0; }
-  return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, C2D_SFX(bundle_fn)(trk, evq),
+  return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, C2D_SFX(bundle_fn)(trk, evq, refl),
                                                            c2d::BLOCK, lds_bytes);
 }
 
@@ -3321,11 +3417,16 @@ extern "C" int C2D_SFX(c2d_aux_occupancy)(int which, int* blocks_per_cu) {
   return (int)e;
 }
 
-extern "C" int C2D_SFX(c2d_transport_occupancy)(int* blocks_per_cu, size_t lds_bytes, int trk) {
-  hipError_t e = trk ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                           blocks_per_cu, C2D_SFX(c2d::c2d_transport_kernel)<1>, c2d::BLOCK, lds_bytes)
+extern "C" int C2D_SFX(c2d_transport_occupancy)(int* blocks_per_cu, size_t lds_bytes, int trk, int refl) {
+  if (refl)
+    return (int)(trk ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                           blocks_per_cu, C2D_SFX(c2d::c2d_transport_kernel)<1, 1>, c2d::BLOCK, lds_bytes)
                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                           blocks_per_cu, C2D_SFX(c2d::c2d_transport_kernel)<0>, c2d::BLOCK, lds_bytes);
+                           blocks_per_cu, C2D_SFX(c2d::c2d_transport_kernel)<0, 1>, c2d::BLOCK, lds_bytes));
+  hipError_t e = trk ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                           blocks_per_cu, C2D_SFX(c2d::c2d_transport_kernel)<1, 0>, c2d::BLOCK, lds_bytes)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                           blocks_per_cu, C2D_SFX(c2d::c2d_transport_kernel)<0, 0>, c2d::BLOCK, lds_bytes);
   return (int)e;
 }
 

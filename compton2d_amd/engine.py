@@ -200,6 +200,15 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_comm_init.argtypes = [vp, C.c_void_p, C.c_int32, C.c_int32]
     lib.c2d_allreduce_tallies.restype = C.c_int
     lib.c2d_allreduce_tallies.argtypes = [vp]
+    lib.c2d_reflect_tables_host.restype = C.c_int
+    lib.c2d_reflect_tables_host.argtypes = [C.POINTER(C.c_double)] * 3
+    lib.c2d_reflect_tables.restype = C.c_int
+    lib.c2d_reflect_tables.argtypes = [vp] + [C.POINTER(C.c_double)] * 3
+    lib.c2d_reflect_result.restype = C.c_int
+    lib.c2d_reflect_result.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]
+    lib.c2d_selftest_reflect.restype = C.c_int
+    lib.c2d_selftest_reflect.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int64,
+                                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if path is None:
         _lib = lib
     return lib
@@ -287,6 +296,25 @@ class Engine:
 
     def tallies(self) -> dict:
         return abi.split_tallies(self.tallies_raw(), self.nz, self.nr, self.nmu)
+
+    # -- Compton reflection (cr_sent != 0) ------------------------------------
+    def reflect_tables(self):
+        """The context's reflection tables from the device (c2d_reflect_tables):
+        E_ref [500], P_ref [n_in, n_out], W_abs [n_in, n_out]; cr_sent 1..3 only."""
+        n = abi.N_REF
+        E, P, W = np.zeros(n), np.zeros((n, n)), np.zeros((n, n))
+        self._check(self.lib.c2d_reflect_tables(self.ctx, E.ctypes.data_as(abi.PD), P.ctypes.data_as(abi.PD),
+                                                W.ctypes.data_as(abi.PD)))
+        return E, P, W
+
+    def reflect_result(self, world_sum: bool = False):
+        """The last step's Ed_ref [nr] and the (specular, matrix, disk) reflection
+        counts (c2d_reflect_result); world_sum sums over the communicator first."""
+        ed = np.zeros(self.nr)
+        cnt = np.zeros(3, np.int64)
+        self._check(self.lib.c2d_reflect_result(self.ctx, ed.ctypes.data_as(abi.PD),
+                                                cnt.ctypes.data_as(C.POINTER(C.c_int64)), int(bool(world_sum))))
+        return ed, cnt
 
     def last_event_count(self) -> int:
         """Escape events the last transport step wrote (c2d_events with no buffer)."""
@@ -847,6 +875,26 @@ def device_fmt_e14_7(x: np.ndarray, device: int = 0) -> np.ndarray:
     if rc != 0:
         raise C2DError(rc, "c2d_selftest_fmt failed")
     return np.frombuffer(out.raw[:14 * x.size], np.uint8).reshape(-1, 14)
+
+
+def device_reflect(boundary: int, cr_sent: int, spec_switch: int, states: np.ndarray, keys: np.ndarray,
+                   device: int = 0):
+    """The kernels' reflection functions on packet states (c2d_selftest_reflect):
+    states [n, 8] = xnu, ew, wmu, rpre, zpre, phi, dcen, tbbl; keys uint64 [n].
+    Returns (out [n, 10] = xnu, ew, wmu, rpre, zpre, t_bound, draws, idead, n_in,
+    n_out; the sum of the scratch Ed_ref)."""
+    lib = load_library()
+    st = np.ascontiguousarray(states, np.float64).reshape(-1, 8)
+    k = np.ascontiguousarray(keys, np.uint64).ravel()
+    assert k.size == st.shape[0]
+    out = np.zeros((st.shape[0], 10))
+    ed = C.c_double()
+    rc = lib.c2d_selftest_reflect(device, int(boundary), int(cr_sent), int(spec_switch), st.ctypes.data_as(abi.PD),
+                                  k.ctypes.data_as(C.POINTER(C.c_uint64)), st.shape[0], out.ctypes.data_as(abi.PD),
+                                  C.byref(ed))
+    if rc != 0:
+        raise C2DError(rc, "c2d_selftest_reflect failed")
+    return out, ed.value
 
 
 def device_scan_e14_7(fields, device: int = 0):

@@ -13,6 +13,9 @@
  *   src/xec2d.f:325/371  xec_add/graphics_collect  c2d_tally_device_ptr + one all-reduce
  *   src/update2d.f:1929  cens_add_up (REDUCE)      c2d_tally_device_ptr + one all-reduce
  *   src/imcleak2d.f:171  event-file writes         c2d_events, c2d_events_write
+ *   src/imcleak2d.f:104-165, :197-275 Compton      c2d_config.cr_sent (inside c2d_transport_step),
+ *     reflection; src/ref_matrix.f Pref_calc,      c2d_reflect_tables_host / c2d_reflect_tables,
+ *     Wref_calc (setup2d.f:40-41); Ed_ref          c2d_reflect_result
  *   postprocessing/pspt.c:245  event-file reads     c2d_events_read, c2d_obs_accumulate_file
  *   src/census2d.f:1-76  write_cens/read_cens      c2d_census_write / c2d_census_read (the files),
  *                                                  c2d_census_export / c2d_census_import (arrays)
@@ -124,7 +127,22 @@ typedef struct c2d_config {
   const double* mu;               /* [nmu] upper bin edges                    */
   int32_t split1, split2, split3, spl3_trg;  /* variance reduction (COMMON /split/) */
   int32_t spec_switch;            /* 0: escaping spectrum into fout            */
-  int32_t cr_sent;                /* Compton reflection; only 0 supported      */
+  /* Compton reflection (imcleak2d.f:104-165, :197-275):
+   *   0  none: every packet at a system boundary leaves
+   *   1  lower boundary: a ring with tbbl > 0 reflects through the matrices
+   *      P_ref / W_abs (new energy and weight, Ed_ref += the new weight,
+   *      wmu = |wmu|), a ring with tbbl <= 0 specularly (wmu = -wmu)
+   *   2  outer r-boundary: a packet with wmu <= 0 is reflected by the disk
+   *      (matrices, zpre = 0, wmu uniform in (0,1)) and leaves with its new
+   *      values; it counts as an escape and writes an event
+   *   3  both 1 and 2
+   *   4  lower boundary, always specular; needs no tables
+   * Probe copies never reflect.  spec_switch = 1 adds the specular branch's
+   * fout line (the spectrum incident on the boundary).  With cr_sent != 0
+   * the bundle kernel's per-wave escape queue stays off (the inline path): a
+   * reflection draws from the packet's stream and queue entries carry no
+   * stream position. */
+  int32_t cr_sent;
   int32_t pair_switch;            /* gamma-gamma; inert in the MPI reference (H6) */
   int32_t kappa_lag;              /* 1: census+volume use previous step's kappa_tot (H3) */
   int32_t comtot_mode;            /* C2D_COMTOT_EXACT | C2D_COMTOT_TABLE       */
@@ -766,6 +784,34 @@ int  c2d_selftest_fmt(int device, const double* x, int64_t n, char* out);
  * C2D_SCAN_SELFTEST_EXACT=1 (environment, read at every call; the event
  * reader honours it too) sends every field through the multi-limb path. */
 int  c2d_selftest_scan(int device, const char* text, int64_t n, double* out, int32_t* status);
+
+/* ---- Compton reflection (c2d_config.cr_sent) ---- */
+#define C2D_NREF 500   /* n_ref: energies of the reflection tables (general.pa) */
+/* The run-constant tables of src/ref_matrix.f built on the host in the
+ * reference's summation order; needs no context and no GPU.  E_ref[500] in
+ * keV; P_ref and W_abs are [n_in][n_out] (500 x 500, n_out fastest: the
+ * reference's P_ref(n_out, n_in) in memory).  Any pointer may be null.
+ * C2D_E_ARG if a P_ref column is not non-decreasing in n_out. */
+int  c2d_reflect_tables_host(double* E_ref, double* P_ref, double* W_abs);
+/* The context's device copies of the same tables (uploaded by c2d_init for
+ * cr_sent 1..3); C2D_E_STATE for cr_sent 0 and 4, which use none. */
+int  c2d_reflect_tables(c2d_ctx* ctx, double* E_ref, double* P_ref, double* W_abs);
+/* The last step's Ed_ref[nr] (imcleak2d.f:155: the reflected weight per lower
+ * ring) and counts[3] = packets reflected specularly, through the matrix at
+ * the lower boundary, and by the disk.  They live beside the tally buffer
+ * (c2d_tally_layout is unchanged) and are zeroed when a step starts.
+ * world_sum != 0 sums over the context's communicator first (c2d_comm_init).
+ * C2D_E_STATE before the first step; zeros with cr_sent = 0. */
+int  c2d_reflect_result(c2d_ctx* ctx, double* Ed_ref, int64_t counts[3], int32_t world_sum);
+/* Diagnostics: the kernels' reflection functions (csrc/c2d_reflect.hpp) on n
+ * packet states.  boundary 0 = lower (one ring), 1 = outer r-boundary; time =
+ * 100, dt = 10; in[8 n] = xnu, ew, wmu, rpre, zpre, phi, dcen, tbbl; stream
+ * (keys[i], sub 0) from counter 0.  out[10 n] = xnu, ew, wmu, rpre, zpre,
+ * t_bound, draws taken, idead, n_in, n_out (1-based; 0 when no matrix lookup
+ * was made); t_bound = time + dt - rad_cp dcen unless the disk reflected.
+ * *Ed_ref_sum = the sum of the scratch Ed_ref the adds went to. */
+int  c2d_selftest_reflect(int device, int boundary, int cr_sent, int spec_switch, const double* in,
+                          const uint64_t* keys, int64_t n, double* out, double* Ed_ref_sum);
 
 #ifdef __cplusplus
 }

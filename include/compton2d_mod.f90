@@ -430,6 +430,45 @@ module compton2d
        integer(c_int32_t), value :: factor, world_sum
      end function c2d_obs_write_pspt
 
+     ! ---- Compton reflection (c2d_config%cr_sent 1..4) ----
+     ! the tables of src/ref_matrix.f on the host: E_ref(500), P_ref(500,500),
+     ! W_abs(500,500) in the reference's own COMMON layout (n_out, n_in)
+     integer(c_int) function c2d_reflect_tables_host(E_ref, P_ref, W_abs) &
+          bind(C, name='c2d_reflect_tables_host')
+       import :: c_int, c_double
+       real(c_double), intent(out) :: E_ref(*), P_ref(*), W_abs(*)
+     end function c2d_reflect_tables_host
+
+     ! the context's device copies (cr_sent 1..3)
+     integer(c_int) function c2d_reflect_tables(ctx, E_ref, P_ref, W_abs) &
+          bind(C, name='c2d_reflect_tables')
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: E_ref(*), P_ref(*), W_abs(*)
+     end function c2d_reflect_tables
+
+     ! the last step's Ed_ref(1:nr) and the specular, matrix and disk counts
+     integer(c_int) function c2d_reflect_result(ctx, Ed_ref, counts, world_sum) &
+          bind(C, name='c2d_reflect_result')
+       import :: c_int, c_ptr, c_double, c_int64_t, c_int32_t
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: Ed_ref(*)
+       integer(c_int64_t), intent(out) :: counts(3)
+       integer(c_int32_t), value :: world_sum
+     end function c2d_reflect_result
+
+     ! diagnostics: the kernels' reflection functions on n packet states
+     integer(c_int) function c2d_selftest_reflect(device, boundary, cr_sent, spec_switch, in, keys, n, &
+          out, Ed_ref_sum) bind(C, name='c2d_selftest_reflect')
+       import :: c_int, c_double, c_int64_t
+       integer(c_int), value :: device, boundary, cr_sent, spec_switch
+       real(c_double), intent(in) :: in(*)
+       integer(c_int64_t), intent(in) :: keys(*)
+       integer(c_int64_t), value :: n
+       real(c_double), intent(out) :: out(*)
+       real(c_double), intent(out) :: Ed_ref_sum
+     end function c2d_selftest_reflect
+
      ! ---- observer sets: up to C2D_OBS_SET_MAX binnings filled in one pass
      !      over the escapes (several pspt SEDs and plcm light curves) ----
      integer(c_int) function c2d_obs_set_clear(ctx) bind(C, name='c2d_obs_set_clear')
