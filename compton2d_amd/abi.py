@@ -128,6 +128,70 @@ def reflect_tables_host():
     return E, P, W
 
 
+def setup_grids():
+    """gnt [NUM_NT], E_field [NPHFIELD], E_ph [N_VOL] as the reference's setup
+    builds them (c2d_setup_grids; host only)."""
+    from . import engine
+    lib = engine.load_library()
+    gnt, E_field, E_ph = np.zeros(NUM_NT), np.zeros(NPHFIELD), np.zeros(N_VOL)
+    lib.c2d_setup_grids(gnt.ctypes.data_as(PD), E_field.ctypes.data_as(PD), E_ph.ctypes.data_as(PD))
+    return gnt, E_field, E_ph
+
+
+def setup_grid_args(gnt, E_field):
+    return (np.ascontiguousarray(gnt, dtype=np.float64).reshape(-1),
+            np.ascontiguousarray(E_field, dtype=np.float64).reshape(-1))
+
+
+def ic_loss_out(n_el: int, n_ph: int, fortran: bool):
+    """An F_IC [n_el, n_ph] to fill and its element strides (s_i, s_ph)."""
+    if fortran:
+        return np.zeros((n_el, n_ph), order="F"), 1, n_el
+    return np.zeros((n_el, n_ph)), n_ph, 1
+
+
+def ic_loss_host(gnt, E_field, libm: bool, fortran: bool = False) -> np.ndarray:
+    """F_IC [n_el, n_ph] of IC_loss (src/icloss2d.f) on one host core
+    (c2d_ic_loss_host): libm=True with the C library's log, libm=False with
+    c2d_log, the flavour the GPU runs."""
+    from . import engine
+    lib = engine.load_library()
+    gnt, E_field = setup_grid_args(gnt, E_field)
+    F, s_i, s_ph = ic_loss_out(gnt.size, E_field.size, fortran)
+    rc = lib.c2d_ic_loss_host(gnt.ctypes.data_as(PD), gnt.size, E_field.ctypes.data_as(PD), E_field.size,
+                              F.ctypes.data_as(PD), s_i, s_ph, int(bool(libm)))
+    if rc != 0:
+        raise engine.C2DError(rc, "c2d_ic_loss_host failed")
+    return F
+
+
+SETUP_ELECTRON_OUT = ("gmin", "N_nth", "gbar_nth", "f_nt", "Pnt")
+
+
+def setup_electron_args(tea, amxwl, gmin, gmax, p_nth):
+    """The five per-zone inputs as equal-length f64 vectors, and zeroed outputs."""
+    ins = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (tea, amxwl, gmin, gmax, p_nth)]
+    n = ins[0].size
+    assert all(a.size == n for a in ins)
+    out = {k: np.zeros(n) for k in SETUP_ELECTRON_OUT[:3]}
+    out["f_nt"], out["Pnt"] = np.zeros((n, NUM_NT)), np.zeros((n, NUM_NT))
+    return ins, out
+
+
+def setup_electrons_host(tea, amxwl, gmin, gmax, p_nth, libm: bool) -> dict:
+    """gam_min and P_nontherm of n zones on the host (c2d_setup_electrons_host):
+    gmin, N_nth, gbar_nth [n], f_nt, Pnt [n, 200]."""
+    from . import engine
+    lib = engine.load_library()
+    ins, out = setup_electron_args(tea, amxwl, gmin, gmax, p_nth)
+    rc = lib.c2d_setup_electrons_host(ins[0].size, *[a.ctypes.data_as(PD) for a in ins],
+                                      *[out[k].ctypes.data_as(PD) for k in SETUP_ELECTRON_OUT],
+                                      int(bool(libm)))
+    if rc != 0:
+        raise engine.C2DError(rc, "c2d_setup_electrons_host failed")
+    return out
+
+
 def tally_layout(nz: int, nr: int, nmu: int) -> dict:
     """Python restatement of c2d_tally_layout_for (include/compton2d.h)."""
     nc = nz * nr

@@ -163,8 +163,8 @@ __global__ void __launch_bounds__(64) c2d_selftest_mcd_kernel(const double* z, c
 }
 }  // namespace c2d
 
-/* the abscissa table as capi.cpp ensure_mcd builds it */
-static std::vector<double> mcd_abscissae() {
+/* the abscissa table as capi.cpp ensure_mcd builds it (setup.hip uses it too) */
+std::vector<double> c2d_mcd_abscissae() {
   std::vector<double> mt((size_t)C2D_FP_MCD_N * 4);
   const double dtm = 1.001, sm = 5.0e-1 * (1.0 + dtm);
   double t = 1.0;
@@ -182,7 +182,7 @@ static std::vector<double> mcd_abscissae() {
 extern "C" int c2d_selftest_mcdonald(int device, const double* z_host, int n, double* out_host) {
   if (n <= 0) return 0;
   if (hipSetDevice(device) != hipSuccess) return -2;
-  const std::vector<double> mt = mcd_abscissae();
+  const std::vector<double> mt = c2d_mcd_abscissae();
   double *z = nullptr, *tab = nullptr, *out = nullptr;
   int rc = 0;
   if (hipMalloc((void**)&z, n * sizeof(double)) != hipSuccess ||
@@ -214,7 +214,7 @@ extern "C" int c2d_fp_mtab_test(const double* mcd, const double* mom, const doub
 extern "C" int c2d_selftest_mcd_fast(int device, const double* z_host, int n, double* out_host) {
   if (n <= 0) return 0;
   if (hipSetDevice(device) != hipSuccess) return -2;
-  const std::vector<double> mt = mcd_abscissae();
+  const std::vector<double> mt = c2d_mcd_abscissae();
   double *z = nullptr, *tab = nullptr, *mom = nullptr, *out = nullptr;
   int rc = 0;
   if (hipMalloc((void**)&z, n * sizeof(double)) != hipSuccess ||

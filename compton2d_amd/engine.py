@@ -209,6 +209,20 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_selftest_reflect.restype = C.c_int
     lib.c2d_selftest_reflect.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int64,
                                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    pd = C.POINTER(C.c_double)
+    lib.c2d_setup_grids.restype = C.c_int
+    lib.c2d_setup_grids.argtypes = [pd] * 3
+    ic = [pd, C.c_int, pd, C.c_int, pd, C.c_int64, C.c_int64]
+    lib.c2d_ic_loss.restype = C.c_int
+    lib.c2d_ic_loss.argtypes = [C.c_int] + ic
+    lib.c2d_ic_loss_timed.restype = C.c_int
+    lib.c2d_ic_loss_timed.argtypes = [C.c_int] + ic + [pd]
+    lib.c2d_ic_loss_host.restype = C.c_int
+    lib.c2d_ic_loss_host.argtypes = ic + [C.c_int]
+    lib.c2d_setup_electrons.restype = C.c_int
+    lib.c2d_setup_electrons.argtypes = [C.c_int, C.c_int64] + [pd] * 10
+    lib.c2d_setup_electrons_host.restype = C.c_int
+    lib.c2d_setup_electrons_host.argtypes = [C.c_int64] + [pd] * 10 + [C.c_int]
     if path is None:
         _lib = lib
     return lib
@@ -911,3 +925,35 @@ def device_scan_e14_7(fields, device: int = 0):
     if rc != 0:
         raise C2DError(rc, "c2d_selftest_scan failed")
     return out.view(np.uint64), st
+
+
+def ic_loss(gnt: np.ndarray, E_field: np.ndarray, device: int = 0, fortran: bool = False,
+            kernel_ms: Optional[list] = None) -> np.ndarray:
+    """F_IC [n_el, n_ph] of IC_loss (src/icloss2d.f) on the GPU (c2d_ic_loss).
+    fortran=True fills a Fortran-ordered F_IC(n_el, n_ph) through the strides
+    (s_i = 1, s_ph = n_el).  kernel_ms: a list that receives the HIP-event time
+    of the series kernel in ms."""
+    lib = load_library()
+    gnt, E_field = abi.setup_grid_args(gnt, E_field)
+    F, s_i, s_ph = abi.ic_loss_out(gnt.size, E_field.size, fortran)
+    ms = C.c_double(0.0)
+    rc = lib.c2d_ic_loss_timed(device, gnt.ctypes.data_as(abi.PD), gnt.size, E_field.ctypes.data_as(abi.PD),
+                               E_field.size, F.ctypes.data_as(abi.PD), s_i, s_ph,
+                               C.byref(ms) if kernel_ms is not None else None)
+    if rc != 0:
+        raise C2DError(rc, "c2d_ic_loss failed")
+    if kernel_ms is not None:
+        kernel_ms.append(ms.value)
+    return F
+
+
+def setup_electrons(tea, amxwl, gmin, gmax, p_nth, device: int = 0) -> dict:
+    """gam_min and P_nontherm (src/gamma1_2d.f, src/nontherm2d.f) of n zones on
+    the GPU (c2d_setup_electrons): gmin, N_nth, gbar_nth [n], f_nt, Pnt [n, 200]."""
+    lib = load_library()
+    ins, out = abi.setup_electron_args(tea, amxwl, gmin, gmax, p_nth)
+    rc = lib.c2d_setup_electrons(device, ins[0].size, *[a.ctypes.data_as(abi.PD) for a in ins],
+                                 *[out[k].ctypes.data_as(abi.PD) for k in abi.SETUP_ELECTRON_OUT])
+    if rc != 0:
+        raise C2DError(rc, "c2d_setup_electrons failed")
+    return out

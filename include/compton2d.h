@@ -813,6 +813,48 @@ int  c2d_reflect_result(c2d_ctx* ctx, double* Ed_ref, int64_t counts[3], int32_t
 int  c2d_selftest_reflect(int device, int boundary, int cr_sent, int spec_switch, const double* in,
                           const uint64_t* keys, int64_t n, double* out, double* Ed_ref_sum);
 
+/* ---- Run setup: what the reference's `setup` computes before the first step ---- */
+/* None of these needs a context.  The *_host calls use no GPU; `libm` != 0
+ * evaluates log/exp/pow with the C library (the reference's bits: F_IC equals
+ * its IC_loss bit for bit, f_nt/Pnt its P_nontherm), `libm` = 0 with the
+ * library's own c2d_log/c2d_exp/c2d_pow, which is what the GPU calls run: a
+ * device call and its host twin with libm = 0 agree bit for bit.
+ * Errors: C2D_E_ARG for a null pointer, a size out of range or a value that
+ * must be positive and is not; C2D_E_NONFINITE for a NaN or Inf input;
+ * C2D_E_FP if a series or loop reaches its iteration cap.  Arguments are
+ * checked before anything is launched or written. */
+/* gnt[C2D_NUM_NT] as P_nontherm builds it (nontherm2d.f:52-100), E_field
+ * [C2D_NPHFIELD] (setup2d.f:216-222), E_ph[C2D_N_VOL] (volume2d.f:53, 96-113);
+ * any pointer may be null.  Host only. */
+int  c2d_setup_grids(double* gnt, double* E_field, double* E_ph);
+/* IC_loss (src/icloss2d.f): F_IC[i_el * s_i + i_ph * s_ph] for i_el < n_el <=
+ * C2D_NUM_NT, i_ph < n_ph <= C2D_NPHFIELD (strides in elements: s_i = 1, s_ph
+ * = num_nt fills a Fortran F_IC(num_nt, nphfield) in place, as c2d_fp_config
+ * takes it).  gnt and E_field must be positive.  Entries of the
+ * Klein-Nishina branch at high photon energy are cancellation residue, some
+ * negative: the reference's table, reproduced as it is. */
+int  c2d_ic_loss(int device, const double* gnt, int n_el, const double* E_field, int n_ph,
+                 double* F_IC, int64_t s_i, int64_t s_ph);
+int  c2d_ic_loss_host(const double* gnt, int n_el, const double* E_field, int n_ph,
+                      double* F_IC, int64_t s_i, int64_t s_ph, int libm);
+/* c2d_ic_loss that also reports the series kernel's HIP-event time in ms
+ * (kernel_ms may be null). */
+int  c2d_ic_loss_timed(int device, const double* gnt, int n_el, const double* E_field, int n_ph,
+                       double* F_IC, int64_t s_i, int64_t s_ph, double* kernel_ms);
+/* gam_min then P_nontherm (src/gamma1_2d.f:2-52, src/nontherm2d.f:20-121, the
+ * ncycle = 0 branch) of n <= C2D_MAXZONE^2 zones on the grid of
+ * c2d_setup_grids: inputs [n]; gmin_out (gmin as gam_min adjusts it), N_nth,
+ * gbar_nth [n]; f_nt, Pnt [n][C2D_NUM_NT].  tea, gmin, gmax must be positive.
+ * p_nth = 1 with amxwl < 1 gives NaN spectra, as in the reference (0/0 in
+ * P_nontherm). */
+int  c2d_setup_electrons(int device, int64_t n, const double* tea, const double* amxwl,
+                         const double* gmin, const double* gmax, const double* p_nth,
+                         double* gmin_out, double* N_nth, double* gbar_nth, double* f_nt, double* Pnt);
+int  c2d_setup_electrons_host(int64_t n, const double* tea, const double* amxwl,
+                              const double* gmin, const double* gmax, const double* p_nth,
+                              double* gmin_out, double* N_nth, double* gbar_nth, double* f_nt,
+                              double* Pnt, int libm);
+
 #ifdef __cplusplus
 }
 #endif

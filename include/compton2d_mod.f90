@@ -439,6 +439,52 @@ module compton2d
        real(c_double), intent(out) :: E_ref(*), P_ref(*), W_abs(*)
      end function c2d_reflect_tables_host
 
+     ! ---- run setup (no context; the *_host calls use no GPU) ----
+     ! gnt(200), E_field(400), E_ph(400) as the reference's setup builds them
+     integer(c_int) function c2d_setup_grids(gnt, E_field, E_ph) bind(C, name='c2d_setup_grids')
+       import :: c_int, c_double
+       real(c_double), intent(out) :: gnt(*), E_field(*), E_ph(*)
+     end function c2d_setup_grids
+
+     ! IC_loss: s_i = 1, s_ph = num_nt fills COMMON F_IC(num_nt, nphfield) in place
+     integer(c_int) function c2d_ic_loss(device, gnt, n_el, E_field, n_ph, F_IC, s_i, s_ph) &
+          bind(C, name='c2d_ic_loss')
+       import :: c_int, c_double, c_int64_t
+       integer(c_int), value :: device, n_el, n_ph
+       real(c_double), intent(in) :: gnt(*), E_field(*)
+       real(c_double), intent(out) :: F_IC(*)
+       integer(c_int64_t), value :: s_i, s_ph
+     end function c2d_ic_loss
+
+     ! libm /= 0: the C library's log (the reference's bits); 0: the GPU's bits
+     integer(c_int) function c2d_ic_loss_host(gnt, n_el, E_field, n_ph, F_IC, s_i, s_ph, libm) &
+          bind(C, name='c2d_ic_loss_host')
+       import :: c_int, c_double, c_int64_t
+       integer(c_int), value :: n_el, n_ph, libm
+       real(c_double), intent(in) :: gnt(*), E_field(*)
+       real(c_double), intent(out) :: F_IC(*)
+       integer(c_int64_t), value :: s_i, s_ph
+     end function c2d_ic_loss_host
+
+     ! gam_min + P_nontherm of n zones; f_nt, Pnt are (200, n) in Fortran order
+     integer(c_int) function c2d_setup_electrons(device, n, tea, amxwl, gmin, gmax, p_nth, gmin_out, &
+          N_nth, gbar_nth, f_nt, Pnt) bind(C, name='c2d_setup_electrons')
+       import :: c_int, c_double, c_int64_t
+       integer(c_int), value :: device
+       integer(c_int64_t), value :: n
+       real(c_double), intent(in) :: tea(*), amxwl(*), gmin(*), gmax(*), p_nth(*)
+       real(c_double), intent(out) :: gmin_out(*), N_nth(*), gbar_nth(*), f_nt(*), Pnt(*)
+     end function c2d_setup_electrons
+
+     integer(c_int) function c2d_setup_electrons_host(n, tea, amxwl, gmin, gmax, p_nth, gmin_out, &
+          N_nth, gbar_nth, f_nt, Pnt, libm) bind(C, name='c2d_setup_electrons_host')
+       import :: c_int, c_double, c_int64_t
+       integer(c_int64_t), value :: n
+       real(c_double), intent(in) :: tea(*), amxwl(*), gmin(*), gmax(*), p_nth(*)
+       real(c_double), intent(out) :: gmin_out(*), N_nth(*), gbar_nth(*), f_nt(*), Pnt(*)
+       integer(c_int), value :: libm
+     end function c2d_setup_electrons_host
+
      ! the context's device copies (cr_sent 1..3)
      integer(c_int) function c2d_reflect_tables(ctx, E_ref, P_ref, W_abs) &
           bind(C, name='c2d_reflect_tables')
