@@ -17,9 +17,14 @@
  *     then the waves' partials in wave order: every thread gets the same
  *     bits, so all scalar control flow stays uniform across the block);
  *   - the cumulative Pnt is a block inclusive scan;
- *   - the 200-row Chang-Cooper system is solved by parallel cyclic reduction
- *     (8 levels, one row per thread, double-buffered in LDS, one barrier per
- *     level) instead of the Thomas recurrence;
+ *   - the 200-row Chang-Cooper system is solved by partitions (spike_solve)
+ *     instead of the Thomas recurrence: each wave reduces its 64 rows by
+ *     cyclic reduction through wave-private LDS for the right-hand side and
+ *     the two spikes that couple it to its neighbours, then every thread
+ *     solves the chain over the wave interfaces (one barrier).  Plain
+ *     parallel cyclic reduction (pcr_solve: 8 levels, one row per thread,
+ *     double-buffered in LDS, one barrier per level) is the C2D_FPF_SPIKE=0
+ *     build; tests/test_gpu_fp_solver.py runs both;
  *   - McDonald's K2/K3 terms are evaluated BS at a time; each series' first
  *     stopping term is found by a block minimum, so the terms added are
  *     exactly the reference's (same stopping index); their sum is a tree.
@@ -961,7 +966,7 @@ __device__ __forceinline__ void fp_zone_fast(const FpParams& P, Blk<BS>& B, cons
   double g_av_next = 0.0, hr_th_c_next = 0.0;
 #ifdef C2D_FP_PROF
   /* section timers (tools/fp_prof.py): zone_diag 0 = gamma_bar incl. memo,
-   * 1 = PCR solve, 2 = whole sub-step loop, 3 = McDonald pairs computed */
+   * 1 = tridiagonal solve, 2 = whole sub-step loop, 3 = McDonald pairs computed */
   long long pf_gb = 0, pf_tri = 0, pf_loop0 = clock64(), pf_t0 = 0, pf_mcd = 0;
   long long pf_sa = 0, pf_sb = 0, pf_sc = 0, pf_s0 = 0;   /* C2D_FP_PROF_SEC sections */
   long long pm_calls = 0, pm_lds = 0, pm_glob = 0;         /* C2D_FP_PROF_MEMO counts */
@@ -1207,7 +1212,7 @@ __device__ __forceinline__ void fp_zone_fast(const FpParams& P, Blk<BS>& B, cons
       ta = -(d_t * (f_bigW[i - 1] * kA));
     }
     PS_END(pf_sb);
-    /* tridag (:2476-2518) by cyclic reduction; clip u(2..num_nt) (:2512) */
+    /* tridag (:2476-2518) by partitions (spike_solve); clip u(2..num_nt) (:2512) */
     PF_BEGIN();
     /* C2D_FPF_SPIKE=0: plain PCR with a barrier per level (measured equal, r04s) */
 #ifndef C2D_FPF_SPIKE
@@ -1475,5 +1480,111 @@ extern "C" int c2d_fp_mtab_test(const double* mcd, const double* mom, const doub
                                 hipStream_t stream) {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(c2d::c2d_fp_mtab_test_kernel, dim3((unsigned)n), dim3(256), 0, stream, mcd, mom, z, out);
+  return (int)hipGetLastError();
+}
+
+namespace c2d {
+namespace {
+/* selftest: the tridiagonal solvers on supplied systems, as fp_zone_fast calls
+ * them: one workgroup, thread t holds row t+1 of a[nsys][NT] .. d[nsys][NT],
+ * the threads past row NT the identity row; the systems one after another with
+ * one barrier between two calls (the zone loop has at least that), so the
+ * solvers' LDS buffers are reused.  x[nsys][BS]: every thread's result. */
+template <int BS>
+__global__ void __launch_bounds__(BS) c2d_fp_solve_test_kernel(int solver, const double* __restrict__ a,
+                                                               const double* __restrict__ b,
+                                                               const double* __restrict__ c,
+                                                               const double* __restrict__ d, int nsys,
+                                                               double* __restrict__ x) {
+  Blk<BS> B;
+  B.tid = threadIdx.x;
+  B.lane = B.tid & (FPB - 1);
+  B.wave = B.tid / FPB;
+  const bool own = B.tid < NT;
+  for (int s = 0; s < nsys; s++) {
+    const size_t o = (size_t)s * NT + B.tid;
+    const double ta = own ? a[o] : 0.0, tb = own ? b[o] : 1.0, tc = own ? c[o] : 0.0, td = own ? d[o] : 0.0;
+    const double u = solver == 0 ? spike_solve<BS>(B, ta, tb, tc, td) : pcr_solve<BS>(B, ta, tb, tc, td);
+    x[(size_t)s * BS + B.tid] = u;
+    __syncthreads();
+  }
+}
+
+/* selftest: one Blk primitive per launch on supplied per-thread values, nvec
+ * vectors one after another through the same Blk (its LDS slots alternate as
+ * in the kernel); every thread's results are written.  op 0 sum2, 1 scan,
+ * 2 scan_sum (doubles in[nvec][BS]); 3 minmax, 4 min2 (int32 in[nvec][BS]);
+ * 5 firsts<TPT> (flag bytes in[nvec][TPT][BS]).  out[nvec][R][BS], R results
+ * per thread: (a, b), (prefix, total), (prefix, total, w), and int32 pairs. */
+template <int BS>
+__global__ void __launch_bounds__(BS) c2d_fp_block_test_kernel(int op, const void* __restrict__ in_a,
+                                                               const void* __restrict__ in_b, int nvec,
+                                                               void* __restrict__ out) {
+  Blk<BS> B;
+  B.tid = threadIdx.x;
+  B.lane = B.tid & (FPB - 1);
+  B.wave = B.tid / FPB;
+  const int t = B.tid;
+  const double *da = (const double*)in_a, *db = (const double*)in_b;
+  const int *ia = (const int*)in_a, *ib = (const int*)in_b;
+  const unsigned char *fa = (const unsigned char*)in_a, *fb = (const unsigned char*)in_b;
+  double* od = (double*)out;
+  int* oi = (int*)out;
+  for (int n = 0; n < nvec; n++) {
+    const size_t v = (size_t)n * BS + t;
+    if (op == 0) {
+      double p = da[v], q = db[v];
+      B.sum2(p, q);
+      od[(size_t)n * 2 * BS + t] = p;
+      od[(size_t)n * 2 * BS + BS + t] = q;
+    } else if (op == 1) {
+      double tot = 0.0;
+      const double p = B.scan(da[v], tot);
+      od[(size_t)n * 2 * BS + t] = p;
+      od[(size_t)n * 2 * BS + BS + t] = tot;
+    } else if (op == 2) {
+      double tot = 0.0, w = db[v];
+      const double p = B.scan_sum(da[v], tot, w);
+      od[(size_t)n * 3 * BS + t] = p;
+      od[(size_t)n * 3 * BS + BS + t] = tot;
+      od[(size_t)n * 3 * BS + 2 * BS + t] = w;
+    } else if (op == 3 || op == 4) {
+      int p = ia[v], q = ib[v];
+      if (op == 3) B.minmax(p, q); else B.min2(p, q);
+      oi[(size_t)n * 2 * BS + t] = p;
+      oi[(size_t)n * 2 * BS + BS + t] = q;
+    } else {
+      bool s2[TPT], s3[TPT];
+#pragma unroll
+      for (int k = 0; k < TPT; k++) {
+        s2[k] = fa[((size_t)n * TPT + k) * BS + t] != 0;
+        s3[k] = fb[((size_t)n * TPT + k) * BS + t] != 0;
+      }
+      int p, q;
+      B.template firsts<TPT>(s2, s3, p, q);
+      oi[(size_t)n * 2 * BS + t] = p;
+      oi[(size_t)n * 2 * BS + BS + t] = q;
+    }
+  }
+}
+}  // namespace
+}  // namespace c2d
+
+extern "C" int c2d_fp_fast_tpt(void) { return C2D_FPF_TPT; }
+
+/* device pointers; x holds nsys * C2D_FPF_BS doubles */
+extern "C" int c2d_fp_solve_test(int solver, const double* a, const double* b, const double* c, const double* d,
+                                 int nsys, double* x, hipStream_t stream) {
+  if (nsys <= 0) return 0;
+  hipLaunchKernelGGL(c2d::c2d_fp_solve_test_kernel<C2D_FPF_BS>, dim3(1), dim3(C2D_FPF_BS), 0, stream, solver, a, b,
+                     c, d, nsys, x);
+  return (int)hipGetLastError();
+}
+
+extern "C" int c2d_fp_block_test(int op, const void* in_a, const void* in_b, int nvec, void* out,
+                                 hipStream_t stream) {
+  if (nvec <= 0) return 0;
+  hipLaunchKernelGGL(c2d::c2d_fp_block_test_kernel<C2D_FPF_BS>, dim3(1), dim3(C2D_FPF_BS), 0, stream, op, in_a, in_b,
+                     nvec, out);
   return (int)hipGetLastError();
 }

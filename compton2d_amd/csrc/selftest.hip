@@ -236,6 +236,72 @@ extern "C" int c2d_selftest_mcd_fast(int device, const double* z_host, int n, do
   return rc;
 }
 
+/* The fast FP kernel's tridiagonal solvers and block primitives on supplied
+ * values (fp_fast.hip c2d_fp_solve_test_kernel / c2d_fp_block_test_kernel),
+ * one workgroup of the library's own block size. */
+extern "C" int c2d_fp_fast_block(int ncell, int n_simd);
+extern "C" int c2d_fp_fast_tpt(void);
+extern "C" int c2d_fp_solve_test(int solver, const double* a, const double* b, const double* c, const double* d,
+                                 int nsys, double* x, hipStream_t stream);
+extern "C" int c2d_fp_block_test(int op, const void* in_a, const void* in_b, int nvec, void* out,
+                                 hipStream_t stream);
+extern "C" int c2d_selftest_fp_dims(int32_t* block, int32_t* tpt) {
+  if (block) *block = c2d_fp_fast_block(1, 1);
+  if (tpt) *tpt = c2d_fp_fast_tpt();
+  return 0;
+}
+
+extern "C" int c2d_selftest_fp_solve(int device, int solver, const double* a_host, const double* b_host,
+                                     const double* c_host, const double* d_host, int nsys, double* x_host) {
+  if (solver < 0 || solver > 1) return -1;
+  if (nsys <= 0) return 0;
+  if (hipSetDevice(device) != hipSuccess) return -2;
+  const size_t nin = (size_t)nsys * C2D_NUM_NT * sizeof(double);
+  const size_t nout = (size_t)nsys * c2d_fp_fast_block(1, 1) * sizeof(double);
+  const double* src[4] = {a_host, b_host, c_host, d_host};
+  double *in[4] = {nullptr, nullptr, nullptr, nullptr}, *x = nullptr;
+  int rc = 0;
+  for (int q = 0; q < 4 && !rc; q++)
+    if (hipMalloc((void**)&in[q], nin) != hipSuccess ||
+        hipMemcpy(in[q], src[q], nin, hipMemcpyHostToDevice) != hipSuccess)
+      rc = -2;
+  if (!rc && (hipMalloc((void**)&x, nout) != hipSuccess || hipMemset(x, 0xff, nout) != hipSuccess)) rc = -2;
+  if (!rc && c2d_fp_solve_test(solver, in[0], in[1], in[2], in[3], nsys, x, 0) != 0) rc = -2;
+  if (!rc && hipDeviceSynchronize() != hipSuccess) rc = -2;
+  if (!rc && hipMemcpy(x_host, x, nout, hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
+  for (int q = 0; q < 4; q++)
+    if (in[q]) (void)hipFree(in[q]);
+  if (x) (void)hipFree(x);
+  return rc;
+}
+
+extern "C" int c2d_selftest_fp_block(int device, int op, const void* a_host, const void* b_host, int nvec,
+                                     void* out_host) {
+  if (op < 0 || op > 5) return -1;
+  if (nvec <= 0) return 0;
+  if (hipSetDevice(device) != hipSuccess) return -2;
+  const size_t bs = (size_t)c2d_fp_fast_block(1, 1);
+  /* bytes per vector: the input of one series, and every thread's results */
+  const size_t ein = op <= 2 ? 8 * bs : (op <= 4 ? 4 * bs : (size_t)c2d_fp_fast_tpt() * bs);
+  const size_t eout = op <= 1 ? 16 * bs : (op == 2 ? 24 * bs : 8 * bs);
+  const size_t nin = ein * (size_t)nvec, nout = eout * (size_t)nvec;
+  const bool two = op != 1;                   /* scan takes one input */
+  void *a = nullptr, *b = nullptr, *out = nullptr;
+  int rc = 0;
+  if (hipMalloc(&a, nin) != hipSuccess || hipMemcpy(a, a_host, nin, hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  if (!rc && two &&
+      (hipMalloc(&b, nin) != hipSuccess || hipMemcpy(b, b_host, nin, hipMemcpyHostToDevice) != hipSuccess))
+    rc = -2;
+  if (!rc && (hipMalloc(&out, nout) != hipSuccess || hipMemset(out, 0xff, nout) != hipSuccess)) rc = -2;
+  if (!rc && c2d_fp_block_test(op, a, b, nvec, out, 0) != 0) rc = -2;
+  if (!rc && hipDeviceSynchronize() != hipSuccess) rc = -2;
+  if (!rc && hipMemcpy(out_host, out, nout, hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
+  if (a) (void)hipFree(a);
+  if (b) (void)hipFree(b);
+  if (out) (void)hipFree(out);
+  return rc;
+}
+
 /* The reflection functions of the transport kernels (c2d_reflect.hpp) on n
  * packet states, one thread each: boundary 0 = the lower boundary (ring 1),
  * 1 = the outer r-boundary; time = C2D_ST_REFL_TIME, dt = C2D_ST_REFL_DT;

@@ -519,7 +519,7 @@ class Engine:
 
     def fp_set_mode(self, mode: int) -> None:
         """abi.FP_EXACT (bit for bit the reference order, default),
-        abi.FP_FAST (block-parallel sums, PCR tridag, tree-summed McDonald
+        abi.FP_FAST (block-parallel sums, partitioned tridag, tree-summed McDonald
         series: equal within rounding) or abi.FP_AUTO (per update: exact while
         every zone sits on the tea clamp within a few sub-steps, fast
         otherwise); include/compton2d.h c2d_fp_set_mode."""
@@ -851,6 +851,68 @@ def device_mcd_fast(z: np.ndarray, device: int = 0) -> np.ndarray:
     rc = lib.c2d_selftest_mcd_fast(device, z.ctypes.data_as(abi.PD), len(z), out.ctypes.data_as(abi.PD))
     if rc != 0:
         raise C2DError(rc, "c2d_selftest_mcd_fast failed")
+    return out
+
+
+def fp_fast_dims():
+    """(block, tpt) of the fast FP kernel: its workgroup size and its McDonald
+    terms per thread per pass (c2d_selftest_fp_dims; needs no GPU)."""
+    lib = load_library()
+    lib.c2d_selftest_fp_dims.restype = C.c_int
+    lib.c2d_selftest_fp_dims.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    bs, tpt = C.c_int32(), C.c_int32()
+    lib.c2d_selftest_fp_dims(C.byref(bs), C.byref(tpt))
+    return bs.value, tpt.value
+
+
+FP_SOLVE_SPIKE, FP_SOLVE_PCR = 0, 1
+
+
+def device_fp_solve(solver: int, a, b, c, d, device: int = 0) -> np.ndarray:
+    """The fast FP kernel's tridiagonal solver (FP_SOLVE_SPIKE: the one it
+    runs, FP_SOLVE_PCR: plain cyclic reduction) on the systems a, b, c, d
+    [nsys, 200], one workgroup solving them one after another
+    (c2d_selftest_fp_solve): x [nsys, block], every thread's result."""
+    lib = load_library()
+    lib.c2d_selftest_fp_solve.restype = C.c_int
+    lib.c2d_selftest_fp_solve.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 4 + \
+        [C.c_int, C.POINTER(C.c_double)]
+    a, b, c, d = (np.ascontiguousarray(v, np.float64) for v in (a, b, c, d))
+    nsys, nt = a.shape
+    if nt != abi.NUM_NT or not (b.shape == c.shape == d.shape == a.shape):
+        raise ValueError("systems are [nsys, %d]" % abi.NUM_NT)
+    x = np.zeros((nsys, fp_fast_dims()[0]))
+    rc = lib.c2d_selftest_fp_solve(device, int(solver), *(v.ctypes.data_as(abi.PD) for v in (a, b, c, d)),
+                                   nsys, x.ctypes.data_as(abi.PD))
+    if rc != 0:
+        raise C2DError(rc, "c2d_selftest_fp_solve failed")
+    return x
+
+
+FP_BLK_SUM2, FP_BLK_SCAN, FP_BLK_SCAN_SUM, FP_BLK_MINMAX, FP_BLK_MIN2, FP_BLK_FIRSTS = range(6)
+
+
+def device_fp_block(op: int, in_a, in_b=None, device: int = 0) -> np.ndarray:
+    """One block primitive of the fast FP kernel on per-thread values
+    (c2d_selftest_fp_block), every thread's results: [nvec, R, block].
+    sum2, scan_sum: float64 in_a, in_b [nvec, block] -> (a, b) / (prefix,
+    total, sum of in_b); scan: in_a -> (prefix, total); minmax, min2: int32
+    -> int32 pairs; firsts: flags [nvec, tpt, block] -> int32 first set terms."""
+    lib = load_library()
+    lib.c2d_selftest_fp_block.restype = C.c_int
+    lib.c2d_selftest_fp_block.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    bs, tpt = fp_fast_dims()
+    tin = np.float64 if op <= FP_BLK_SCAN_SUM else (np.int32 if op <= FP_BLK_MIN2 else np.uint8)
+    shape = (tpt, bs) if op == FP_BLK_FIRSTS else (bs,)
+    a = np.ascontiguousarray(in_a, tin)
+    b = a if in_b is None and op == FP_BLK_SCAN else np.ascontiguousarray(in_b, tin)
+    if a.shape[1:] != shape or b.shape != a.shape:
+        raise ValueError("op %d takes [nvec, %s]" % (op, ", ".join(map(str, shape))))
+    nres = 3 if op == FP_BLK_SCAN_SUM else 2
+    out = np.zeros((a.shape[0], nres, bs), np.float64 if op <= FP_BLK_SCAN_SUM else np.int32)
+    rc = lib.c2d_selftest_fp_block(device, int(op), a.ctypes.data, b.ctypes.data, a.shape[0], out.ctypes.data)
+    if rc != 0:
+        raise C2DError(rc, "c2d_selftest_fp_block failed")
     return out
 
 

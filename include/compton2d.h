@@ -577,7 +577,10 @@ int  c2d_fp_step(c2d_ctx* ctx, const c2d_fp_step_in* in, c2d_fp_step_out* out);
  *     McDonald's series in the reference's order -- bit for bit the det-math
  *     oracle (one in-order latency chain per zone);
  *   C2D_FP_FAST: the same per-bin and per-term arithmetic, the sums as block
- *     reductions/scans, tridag by parallel cyclic reduction, McDonald's terms
+ *     reductions/scans, tridag by partitions (each wave reduces its 64 rows by
+ *     cyclic reduction with two coupling spikes, then a chain over the wave
+ *     interfaces; plain parallel cyclic reduction, 8 levels with a barrier
+ *     each, is the C2D_FPF_SPIKE=0 build), McDonald's terms
  *     summed as a tree (the same terms: the reference's stopping index) --
  *     equal to the exact mode within rounding (DESIGN.md §4b states the
  *     tolerance: f_nt 1e-10 relative, Te_new on the same 1.005 lattice);
@@ -772,6 +775,31 @@ int  c2d_selftest_geom(int device, int nr, const double* in, double* out, int64_
  * answered, shader cycles of the table's gamma_bar and of the series,
  * gamma_bar = K3/K2 - 1/z as the fast kernel forms it from the table). */
 int  c2d_selftest_mcd_fast(int device, const double* z, int n, double* out);
+/* Diagnostics: the fast FP kernel's workgroup size (C2D_FPF_BS) and its
+ * McDonald terms per thread per pass (C2D_FPF_TPT), which shape the arrays of
+ * the two entries below.  Either pointer may be null. */
+int  c2d_selftest_fp_dims(int32_t* block, int32_t* tpt);
+/* Diagnostics: the fast FP kernel's tridiagonal solvers (solver 0: the
+ * partitioned solver it runs, 1: plain parallel cyclic reduction) on nsys
+ * systems a x_{i-1} + b x_i + c x_{i+1} = d of C2D_NUM_NT rows, arrays
+ * [nsys][C2D_NUM_NT]: one workgroup of `block` threads solves them one after
+ * another as the kernel's sub-steps do, thread t holding row t+1 and the
+ * threads past the last row the identity row.  x[nsys][block]: every thread's
+ * result (0 past the last row). */
+int  c2d_selftest_fp_solve(int device, int solver, const double* a, const double* b, const double* c,
+                           const double* d, int nsys, double* x);
+/* Diagnostics: one of the fast FP kernel's block primitives on nvec vectors
+ * of per-thread values, one workgroup of `block` threads taking them one after
+ * another; every thread's results are returned.
+ *   op 0 sum2:     double in_a, in_b [nvec][block] -> double out[nvec][2][block]
+ *   op 1 scan:     double in_a (in_b unused)       -> (prefix, total)
+ *   op 2 scan_sum: double in_a (scanned), in_b (summed) -> out[nvec][3][block]
+ *                  (prefix, total, sum of in_b)
+ *   op 3 minmax:   int32 in_a, in_b -> int32 out[nvec][2][block] (min a, max b)
+ *   op 4 min2:     int32 in_a, in_b -> (min a, min b)
+ *   op 5 firsts:   flag bytes in_a, in_b [nvec][tpt][block], term k*block + t
+ *                  at [k][t] -> int32 (first set term of a, of b; INT_MAX: none) */
+int  c2d_selftest_fp_block(int device, int op, const void* in_a, const void* in_b, int nvec, void* out);
 /* Diagnostics: Fortran E14.7 of n doubles on the GPU (csrc/c2d_fmt.h as the
  * event writer runs it), 14 bytes each at out + 14 i, no terminator.
  * C2D_E_NONFINITE if a value is NaN or Inf (its 14 bytes are then '#').
