@@ -10,30 +10,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "c2d_textparse.hpp"   /* c2d_cens_times, c2d_cens_sink */
+
 #define C2D_CENS_BLOCK 256   /* records per workgroup (29 696 B of text = 1 856 x 16 B) */
 
 struct c2d_cens_file;   /* staging buffers of both directions, the powers-of-ten table on the device */
 
-/* times and counts of the last c2d_censtext_write / c2d_censtext_read */
-struct c2d_cens_times {
-  double io_ms;       /* host: fwrite / read of the text and the keys                     */
-  double wait_ms;     /* host: waiting for a chunk                                        */
-  double kernel_ms;   /* device: the format or parse kernels                              */
-  double conv_ms;     /* device: the record conversion (write: the source, both passes, and
-                         the non-finite scan; read: added by the sink's owner)            */
-  int64_t device_records, host_records;   /* read: parsed by the kernel / by the host parser */
-  int32_t chunks;
-};
-
 /* Queues, on the writer's stream, the work that fills records [first,
  * first + n) into the device arrays d6 [n][6], i5 [n][5], keys [n]. */
 typedef int (*c2d_cens_source)(void* user, int64_t first, int64_t n, double* d6, int32_t* i5, uint64_t* keys);
-/* Takes n records in file order, in device memory (on_device != 0: valid until
- * the sink returns and work it queued on the reader's stream has run) or in
- * host memory.  A non-zero return ends the read and is passed on. */
-typedef int (*c2d_cens_sink)(void* user, const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
-                             int on_device);
-
 /* n records to `path` and `path`.keys.  src != NULL: it supplies them chunk by
  * chunk (twice: the non-finite scan runs before either file is opened);
  * src == NULL: they are the host arrays h_d6, h_i5, h_keys. */

@@ -8,25 +8,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "c2d_textparse.hpp"   /* c2d_evr_times, c2d_evr_sink */
+
 struct c2d_evt_reader;   /* staging buffers, the powers-of-ten table on the device */
-
-/* times and counts of the last c2d_evparse_file */
-struct c2d_evr_times {
-  double io_ms;            /* read() of the text                                 */
-  double wait_ms;          /* host waiting for a chunk's copy and parse kernel   */
-  double kernel_ms;        /* the parse kernels                                  */
-  double host_parse_ms;    /* the host parser of what is not canonical           */
-  int64_t canonical;       /* records parsed on the device                       */
-  int64_t host_parsed;     /* records parsed on the host                         */
-  int64_t exact_fields;    /* fields the device decided by the multi-limb path   */
-  int32_t chunks;          /* device chunks                                      */
-};
-
-/* Takes n events in file order: in device memory (on_device != 0; valid
- * until the sink returns, and until work the sink queues on the reader's
- * stream has run) or in host memory.  A non-zero return ends the read and
- * is passed on. */
-typedef int (*c2d_evr_sink)(void* user, const double* events, int64_t n, int on_device);
 
 /* Parse `path` and hand its records to `sink` in order (sink == NULL only
  * counts).  *n_records = the records delivered, also when the call fails.

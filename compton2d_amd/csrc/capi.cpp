@@ -3414,14 +3414,18 @@ extern "C" int c2d_last_events_write_ms(c2d_ctx* c, double* scan_ms, double* ker
 /* ------------------------------------------------------------------------
  * p###_evb.dat text back to events, parsed on the device (evparse.hip)
  * ---------------------------------------------------------------------- */
+/* a non-zero rc of a text-file call: its message if it left one, else our failed sink's or source's own */
+static int file_fail(c2d_ctx* c, int rc, const char* err) {
+  return rc ? (err[0] ? fail(c, rc, "%s", err) : rc) : C2D_OK;
+}
+
 static int events_parse(c2d_ctx* c, const char* path, c2d_evr_sink sink, void* user, int64_t* n) {
   char err[768] = "";
   int64_t got = 0;
   const int rc = c2d_evparse_file(&c->evr, c->cfg.device, c->stream, path, sink, user, &got, &c->evr_times, err,
                                   sizeof err);
   if (n) *n = got;
-  /* a sink that failed has left its own message */
-  return rc ? (err[0] ? fail(c, rc, "%s", err) : rc) : C2D_OK;
+  return file_fail(c, rc, err);
 }
 
 namespace {
@@ -3555,11 +3559,6 @@ __global__ void __launch_bounds__(256) c2d_census_encode_kernel(const double* __
   }
 }
 
-static int census_file_fail(c2d_ctx* c, int rc, const char* err) {
-  /* a callback that failed has left its own message */
-  return rc ? (err[0] ? fail(c, rc, "%s", err) : rc) : C2D_OK;
-}
-
 /* records [first, first + n) of the census as plain records, on the stream */
 static int census_write_source(void* user, int64_t first, int64_t n, double* d6, int32_t* i5, uint64_t* keys) {
   c2d_ctx* c = static_cast<c2d_ctx*>(user);
@@ -3581,7 +3580,7 @@ extern "C" int c2d_census_write(c2d_ctx* c, const char* path, int64_t* n_written
   const int rc = c2d_censtext_write(&c->cfile, c->cfg.device, c->stream, census_write_source, c, nullptr, nullptr,
                                     nullptr, c->n_census, path, &c->cens_times, err, sizeof err);
   if (!rc && n_written) *n_written = c->n_census;
-  return census_file_fail(c, rc, err);
+  return file_fail(c, rc, err);
 }
 
 extern "C" int c2d_census_write_from(c2d_ctx* c, const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
@@ -3591,7 +3590,7 @@ extern "C" int c2d_census_write_from(c2d_ctx* c, const double* d6, const int32_t
   char err[768] = "";
   const int rc = c2d_censtext_write(&c->cfile, c->cfg.device, c->stream, nullptr, nullptr, d6, i5, keys, n, path,
                                     &c->cens_times, err, sizeof err);
-  return census_file_fail(c, rc, err);
+  return file_fail(c, rc, err);
 }
 
 namespace {
@@ -3638,7 +3637,7 @@ extern "C" int c2d_census_read_records(c2d_ctx* c, const char* path, double* d6,
   char err[768] = "";
   const int rc = c2d_censtext_read(&c->cfile, c->cfg.device, c->stream, path, cap > 0 ? census_records_sink : nullptr,
                                    &d, n, &c->cens_times, err, sizeof err);
-  return census_file_fail(c, rc, err);
+  return file_fail(c, rc, err);
 }
 
 /* n plain records (device memory) behind the census, through c2d_census_append */
@@ -3740,7 +3739,7 @@ extern "C" int c2d_census_read(c2d_ctx* c, const char* path, int64_t* n) {
   c->cens_times = T;
   if (n) *n = rc ? 0 : got;
   if (rc) {
-    rc = census_file_fail(c, rc, err);
+    rc = file_fail(c, rc, err);
     if (d.storing) {   /* the previous census is gone and the file's is incomplete */
       c->n_census = 0;
       if (c->chunked) c->n_clist = 0;

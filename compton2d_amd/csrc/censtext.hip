@@ -28,31 +28,18 @@
  * says: every address is a function of the record count alone.
  *
  * What the device does not take (the first record that is not canonical and
- * everything after it, or a tail shorter than a record) goes through a host
- * parser with read_census's rules (compton2d_amd/census_io.py): CR stripped,
+ * everything after it, or a tail shorter than a record) goes through the host
+ * parser of c2d_textparse.hpp with read_census's rules (compton2d_amd/census_io.py): CR stripped,
  * blank lines skipped, fixed 14- and 5-column fields, the E-less three-digit
  * exponent repaired, D or a lower-case e as the exponent letter, a missing
  * final newline.
  */
 #include "c2d_censtext.hpp"
 
-#include <errno.h>
 #include <fcntl.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <sys/stat.h>
-#include <unistd.h>
 
-#include <algorithm>
-#include <chrono>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "../../include/compton2d.h"
-#include "c2d_censfmt.h"
+#include "c2d_textio.hpp"
 
 namespace c2d {
 
@@ -206,108 +193,54 @@ c2d_censparse_kernel(const unsigned char* __restrict__ text, int64_t nrec, int64
   if (tid == 0 && wg_bad != 0xffffffffu) atomicMin(&st->first_bad, (unsigned long long)(r0 + wg_bad));
 }
 
-/* the powers-of-ten table, built once per process */
-static const c2d_fmt_tab* cens_tab() {
-  static c2d_fmt_tab tab;
-  static std::once_flag once;
-  std::call_once(once, [] { c2d_fmt_tab_build(&tab); });
-  return &tab;
-}
-
 }  // namespace c2d
 
 using namespace c2d;
 
 struct c2d_cens_file {
-  int device = 0;
-  c2d_fmt_tab* tab_d = nullptr;
-  CensStat* stat_d = nullptr;
-  CensStat* stat_h = nullptr;            /* pinned: [3], the last one the initial value */
-  unsigned char* text_d = nullptr;       /* cap records of text, rounded up to 16 bytes and 16 beyond */
+  TextStage<CensStat> st;                /* the text padded: both kernels move whole 16-byte vectors */
   double* d6_d = nullptr;                /* cap plain records */
   int32_t* i5_d = nullptr;
   uint64_t* keys_d = nullptr;
-  unsigned char* pin[2] = {nullptr, nullptr};   /* pinned host staging: text ...  */
-  uint64_t* kpin[2] = {nullptr, nullptr};       /* ... and keys, cap records each */
-  int64_t cap = 0;
-  hipEvent_t done[2] = {nullptr, nullptr}, ka[2] = {nullptr, nullptr}, kb[2] = {nullptr, nullptr},
-             kc[2] = {nullptr, nullptr};
+  uint64_t* kpin[2] = {nullptr, nullptr};   /* pinned host staging of the keys, cap records each */
+  hipEvent_t kc[2] = {nullptr, nullptr};    /* before a chunk's conversion */
 };
 
 namespace {
 
-int efail(char* err, size_t n, int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  if (err && n) vsnprintf(err, n, fmt, ap);
-  va_end(ap);
-  return code;
+constexpr CensStat CENS_STAT0 = {0ull, ~0ull};   /* nothing met yet */
+
+void free_records(c2d_cens_file* w) {
+  if (w->d6_d) (void)hipFree(w->d6_d);
+  if (w->i5_d) (void)hipFree(w->i5_d);
+  if (w->keys_d) (void)hipFree(w->keys_d);
+  w->d6_d = nullptr;
+  w->i5_d = nullptr;
+  w->keys_d = nullptr;
+  for (int b = 0; b < 2; b++) {
+    if (w->kpin[b]) (void)hipHostFree(w->kpin[b]);
+    w->kpin[b] = nullptr;
+  }
 }
 
-#define CFCHK(x)                                                                              \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess)                                                                     \
-      return efail(err, errlen, C2D_E_HIP, "%s:%d %s: %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); \
-  } while (0)
-
-/* records per chunk: C2D_CENSTEXT_CHUNK, read at every call (a test knob) */
-int64_t chunk_records() {
-  const char* e = getenv("C2D_CENSTEXT_CHUNK");
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v >= 1) return (int64_t)std::min<long long>(v, 1ll << 24);
+/* the file's stage on first use, with room for `records` */
+int ensure(c2d_cens_file** pw, int device, int64_t records, char* err, size_t errlen) {
+  if (!*pw) {
+    *pw = new c2d_cens_file;
+    (*pw)->st.device = device;
   }
-  return (int64_t)1 << 20;
-}
-
-size_t text_bytes(int64_t records) { return (((size_t)records * C2D_CENS_RECORD + 15) & ~(size_t)15) + 16; }
-
-int ensure(c2d_cens_file* w, int64_t records, char* err, size_t errlen) {
-  if (!w->tab_d) {
-    CFCHK(hipMalloc((void**)&w->tab_d, sizeof(c2d_fmt_tab)));
-    CFCHK(hipMemcpy(w->tab_d, cens_tab(), sizeof(c2d_fmt_tab), hipMemcpyHostToDevice));
-    CFCHK(hipMalloc((void**)&w->stat_d, sizeof(CensStat)));
-    CFCHK(hipHostMalloc((void**)&w->stat_h, 3 * sizeof(CensStat), hipHostMallocDefault));
-    for (int b = 0; b < 2; b++) {
-      CFCHK(hipEventCreateWithFlags(&w->done[b], hipEventDisableTiming));
-      CFCHK(hipEventCreate(&w->ka[b]));
-      CFCHK(hipEventCreate(&w->kb[b]));
-      CFCHK(hipEventCreate(&w->kc[b]));
-    }
-  }
-  if (records > w->cap) {
-    if (w->text_d) (void)hipFree(w->text_d);
-    if (w->d6_d) (void)hipFree(w->d6_d);
-    if (w->i5_d) (void)hipFree(w->i5_d);
-    if (w->keys_d) (void)hipFree(w->keys_d);
-    for (int b = 0; b < 2; b++) {
-      if (w->pin[b]) (void)hipHostFree(w->pin[b]);
-      if (w->kpin[b]) (void)hipHostFree(w->kpin[b]);
-      w->pin[b] = nullptr;
-      w->kpin[b] = nullptr;
-    }
-    w->text_d = nullptr;
-    w->d6_d = nullptr;
-    w->i5_d = nullptr;
-    w->keys_d = nullptr;
-    w->cap = 0;
-    CFCHK(hipMalloc((void**)&w->text_d, text_bytes(records)));
-    CFCHK(hipMemset(w->text_d, ' ', text_bytes(records)));   /* the pad is never parsed; keep it defined */
-    CFCHK(hipMalloc((void**)&w->d6_d, (size_t)records * 6 * sizeof(double)));
-    CFCHK(hipMalloc((void**)&w->i5_d, (size_t)records * 5 * sizeof(int32_t)));
-    CFCHK(hipMalloc((void**)&w->keys_d, (size_t)records * sizeof(uint64_t)));
-    for (int b = 0; b < 2; b++) {
-      CFCHK(hipHostMalloc((void**)&w->pin[b], (size_t)records * C2D_CENS_RECORD, hipHostMallocDefault));
-      CFCHK(hipHostMalloc((void**)&w->kpin[b], (size_t)records * sizeof(uint64_t), hipHostMallocDefault));
-    }
-    w->cap = records;
-  }
-  return C2D_OK;
-}
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  c2d_cens_file* w = *pw;
+  for (int b = 0; b < 2; b++)
+    if (!w->kc[b]) C2D_TXCHK(hipEventCreate(&w->kc[b]));
+  return w->st.ensure(records, C2D_CENS_RECORD, true, [&](int64_t n) {
+    free_records(w);
+    C2D_TXCHK(hipMalloc((void**)&w->d6_d, (size_t)n * 6 * sizeof(double)));
+    C2D_TXCHK(hipMalloc((void**)&w->i5_d, (size_t)n * 5 * sizeof(int32_t)));
+    C2D_TXCHK(hipMalloc((void**)&w->keys_d, (size_t)n * sizeof(uint64_t)));
+    for (int b = 0; b < 2; b++)
+      C2D_TXCHK(hipHostMalloc((void**)&w->kpin[b], (size_t)n * sizeof(uint64_t), hipHostMallocDefault));
+    return C2D_OK;
+  }, err, errlen);
 }
 
 int nonfinite_error(unsigned long long count, unsigned long long first, char* err, size_t errlen) {
@@ -320,63 +253,44 @@ int nonfinite_error(unsigned long long count, unsigned long long first, char* er
 int fill(c2d_cens_file* w, hipStream_t stream, c2d_cens_source src, void* user, const double* h_d6,
          const int32_t* h_i5, const uint64_t* h_keys, int64_t c0, int64_t m, char* err, size_t errlen) {
   if (src) return src(user, c0, m, w->d6_d, w->i5_d, w->keys_d);
-  CFCHK(hipMemcpyAsync(w->d6_d, h_d6 + c0 * 6, (size_t)m * 6 * sizeof(double), hipMemcpyHostToDevice, stream));
-  CFCHK(hipMemcpyAsync(w->i5_d, h_i5 + c0 * 5, (size_t)m * 5 * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-  CFCHK(hipMemcpyAsync(w->keys_d, h_keys + c0, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  C2D_TXCHK(hipMemcpyAsync(w->d6_d, h_d6 + c0 * 6, (size_t)m * 6 * sizeof(double), hipMemcpyHostToDevice, stream));
+  C2D_TXCHK(hipMemcpyAsync(w->i5_d, h_i5 + c0 * 5, (size_t)m * 5 * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  C2D_TXCHK(hipMemcpyAsync(w->keys_d, h_keys + c0, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
   return C2D_OK;
 }
 
 /* the chunks of [0, n) through the pinned buffers into the two files */
-int write_chunks(c2d_cens_file* w, hipStream_t stream, c2d_cens_source src, void* user, const double* h_d6,
-                 const int32_t* h_i5, const uint64_t* h_keys, int64_t n, int64_t chunk, FILE* f, FILE* fk,
-                 const char* path, c2d_cens_times* T, char* err, size_t errlen) {
-  const int64_t nchunks = (n + chunk - 1) / chunk;
-  w->stat_h[2].nonfinite = 0ull;
-  w->stat_h[2].first_bad = ~0ull;
-  CFCHK(hipMemcpyAsync(w->stat_d, &w->stat_h[2], sizeof(CensStat), hipMemcpyHostToDevice, stream));
-  for (int64_t k = 0; k <= nchunks; k++) {
-    if (k < nchunks) {   /* chunk k: convert, format, copy to the pinned buffers k % 2 */
-      const int b = (int)(k & 1);
-      const int64_t c0 = k * chunk, m = std::min(n, c0 + chunk) - c0;
-      CFCHK(hipEventRecord(w->kc[b], stream));
-      { const int rc = fill(w, stream, src, user, h_d6, h_i5, h_keys, c0, m, err, errlen); if (rc) return rc; }
-      CFCHK(hipEventRecord(w->ka[b], stream));
+int write_records(c2d_cens_file* w, hipStream_t stream, c2d_cens_source src, void* user, const double* h_d6,
+                  const int32_t* h_i5, const uint64_t* h_keys, int64_t n, int64_t chunk, FILE* f, FILE* fk,
+                  const char* path, c2d_cens_times* T, char* err, size_t errlen) {
+  TextStage<CensStat>& st = w->st;
+  auto produce = [&](int b, int64_t c0, int64_t m) {   /* convert, format */
+    C2D_TXCHK(hipEventRecord(w->kc[b], stream));
+    { const int rc = fill(w, stream, src, user, h_d6, h_i5, h_keys, c0, m, err, errlen); if (rc) return rc; }
+    return st.timed(stream, b, [&] {
       hipLaunchKernelGGL(c2d_censtext_kernel, dim3((unsigned)((m + C2D_CENS_BLOCK - 1) / C2D_CENS_BLOCK)),
-                         dim3(C2D_CENS_BLOCK), 0, stream, w->d6_d, w->i5_d, w->keys_d, m, w->tab_d, w->text_d,
-                         w->stat_d);
-      CFCHK(hipGetLastError());
-      CFCHK(hipEventRecord(w->kb[b], stream));
-      CFCHK(hipMemcpyAsync(w->pin[b], w->text_d, (size_t)m * C2D_CENS_RECORD, hipMemcpyDeviceToHost, stream));
-      CFCHK(hipMemcpyAsync(w->kpin[b], w->keys_d, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-      CFCHK(hipMemcpyAsync(&w->stat_h[b], w->stat_d, sizeof(CensStat), hipMemcpyDeviceToHost, stream));
-      CFCHK(hipEventRecord(w->done[b], stream));
+                         dim3(C2D_CENS_BLOCK), 0, stream, w->d6_d, w->i5_d, w->keys_d, m, st.tab_d, st.text_d,
+                         st.stat_d);
+    }, err, errlen);
+  };
+  auto copy_out = [&](int b, int64_t m) {
+    C2D_TXCHK(hipMemcpyAsync(w->kpin[b], w->keys_d, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    return C2D_OK;
+  };
+  auto counts = [&](int b) {
+    float ms = 0.f;
+    if (src) {
+      (void)hipEventElapsedTime(&ms, w->kc[b], st.ka[b]);
+      T->conv_ms += ms;
     }
-    if (k > 0) {   /* chunk k - 1: to the files while chunk k is formatted and copied */
-      const int b = (int)((k - 1) & 1);
-      const int64_t c0 = (k - 1) * chunk, m = std::min(n, c0 + chunk) - c0;
-      const double t0 = now_ms();
-      CFCHK(hipEventSynchronize(w->done[b]));
-      const double t1 = now_ms();
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, w->ka[b], w->kb[b]);
-      T->kernel_ms += ms;
-      if (src) {
-        (void)hipEventElapsedTime(&ms, w->kc[b], w->ka[b]);
-        T->conv_ms += ms;
-      }
-      T->wait_ms += t1 - t0;
-      T->chunks++;
-      if (w->stat_h[b].nonfinite)   /* the scan found none: the records changed under the call */
-        return efail(err, errlen, C2D_E_STATE, "census: a non-finite value appeared while '%s' was written", path);
-      const size_t bytes = (size_t)m * C2D_CENS_RECORD;
-      if (fwrite(w->pin[b], 1, bytes, f) != bytes)
-        return efail(err, errlen, C2D_E_IO, "census: cannot write '%s': %s", path, strerror(errno));
-      if (fwrite(w->kpin[b], sizeof(uint64_t), (size_t)m, fk) != (size_t)m)
-        return efail(err, errlen, C2D_E_IO, "census: cannot write '%s.keys': %s", path, strerror(errno));
-      T->io_ms += now_ms() - t1;
-    }
-  }
-  return C2D_OK;
+  };
+  auto write_side = [&](int b, int64_t m) {
+    if (fwrite(w->kpin[b], sizeof(uint64_t), (size_t)m, fk) != (size_t)m)
+      return efail(err, errlen, C2D_E_IO, "census: cannot write '%s.keys': %s", path, strerror(errno));
+    return C2D_OK;
+  };
+  return write_chunks(st, stream, f, "census", path, C2D_CENS_RECORD, n, chunk, CENS_STAT0, T, produce, copy_out,
+                      counts, write_side, err, errlen);
 }
 
 /* NaN/Inf in the records, before either file is opened */
@@ -389,25 +303,24 @@ int scan_records(c2d_cens_file* w, hipStream_t stream, c2d_cens_source src, void
       if (((u[i] >> 52) & 0x7ffu) == 0x7ffu && bad++ == 0) first = (unsigned long long)i;
     return bad ? nonfinite_error(bad, first, err, errlen) : C2D_OK;
   }
-  w->stat_h[2].nonfinite = 0ull;
-  w->stat_h[2].first_bad = ~0ull;
-  CFCHK(hipMemcpyAsync(w->stat_d, &w->stat_h[2], sizeof(CensStat), hipMemcpyHostToDevice, stream));
-  CFCHK(hipEventRecord(w->kc[0], stream));
+  TextStage<CensStat>& st = w->st;
+  { const int rc = st.reset(stream, CENS_STAT0, err, errlen); if (rc) return rc; }
+  C2D_TXCHK(hipEventRecord(w->kc[0], stream));
   for (int64_t c0 = 0; c0 < n; c0 += chunk) {
     const int64_t m = std::min(chunk, n - c0);
     { const int rc = src(user, c0, m, w->d6_d, w->i5_d, w->keys_d); if (rc) return rc; }
     const unsigned grid = (unsigned)std::min<int64_t>((6 * m + 255) / 256, 4096);
     hipLaunchKernelGGL(c2d_censscan_kernel, dim3(grid), dim3(256), 0, stream,
-                       reinterpret_cast<const uint64_t*>(w->d6_d), m, c0, w->stat_d);
-    CFCHK(hipGetLastError());
+                       reinterpret_cast<const uint64_t*>(w->d6_d), m, c0, st.stat_d);
+    C2D_TXCHK(hipGetLastError());
   }
-  CFCHK(hipEventRecord(w->ka[0], stream));
-  CFCHK(hipMemcpyAsync(&w->stat_h[0], w->stat_d, sizeof(CensStat), hipMemcpyDeviceToHost, stream));
-  CFCHK(hipStreamSynchronize(stream));
+  C2D_TXCHK(hipEventRecord(st.ka[0], stream));
+  C2D_TXCHK(hipMemcpyAsync(&st.stat_h[0], st.stat_d, sizeof(CensStat), hipMemcpyDeviceToHost, stream));
+  C2D_TXCHK(hipStreamSynchronize(stream));
   float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, w->kc[0], w->ka[0]);
+  (void)hipEventElapsedTime(&ms, w->kc[0], st.ka[0]);
   T->conv_ms += ms;
-  if (w->stat_h[0].nonfinite) return nonfinite_error(w->stat_h[0].nonfinite, w->stat_h[0].first_bad, err, errlen);
+  if (st.stat_h[0].nonfinite) return nonfinite_error(st.stat_h[0].nonfinite, st.stat_h[0].first_bad, err, errlen);
   return C2D_OK;
 }
 
@@ -425,15 +338,10 @@ extern "C" int c2d_censtext_write(c2d_cens_file** pw, int device, hipStream_t st
                                   const char* path, c2d_cens_times* times, char* err, size_t errlen) {
   c2d_cens_times T = {};
   const std::string kpath = std::string(path) + ".keys";
-  const int64_t chunk = chunk_records();
+  const int64_t chunk = chunk_env("C2D_CENSTEXT_CHUNK", 1ll << 24);
   if (n > 0) {
-    if (!*pw) {
-      *pw = new c2d_cens_file;
-      (*pw)->device = device;
-    }
-    c2d_cens_file* w = *pw;
-    { const int rc = ensure(w, std::min(chunk, n), err, errlen); if (rc) return rc; }
-    { const int rc = scan_records(w, stream, src, user, h_d6, n, chunk, &T, err, errlen);
+    { const int rc = ensure(pw, device, std::min(chunk, n), err, errlen); if (rc) return rc; }
+    { const int rc = scan_records(*pw, stream, src, user, h_d6, n, chunk, &T, err, errlen);
       if (rc) { (void)hipStreamSynchronize(stream); return rc; } }
   }
   FILE* f = fopen(path, "wb");
@@ -448,281 +356,13 @@ extern "C" int c2d_censtext_write(c2d_cens_file** pw, int device, hipStream_t st
   setvbuf(fk, nullptr, _IONBF, 0);
   int rc = C2D_OK;
   if (n > 0) {
-    rc = write_chunks(*pw, stream, src, user, h_d6, h_i5, h_keys, n, chunk, f, fk, path, &T, err, errlen);
+    rc = write_records(*pw, stream, src, user, h_d6, h_i5, h_keys, n, chunk, f, fk, path, &T, err, errlen);
     if (rc) (void)hipStreamSynchronize(stream);   /* nothing in flight into the staging buffers */
   }
   rc = close_both(f, fk, rc, path, err, errlen);
   if (times) *times = T;
   return rc;
 }
-
-namespace {
-
-/* up to `want` bytes, short only at the end of the file; -1 on error */
-int64_t read_full(int fd, void* buf, int64_t want) {
-  int64_t got = 0;
-  while (got < want) {
-    const ssize_t k = read(fd, (unsigned char*)buf + got, (size_t)std::min<int64_t>(want - got, (int64_t)1 << 30));
-    if (k < 0) {
-      if (errno == EINTR) continue;
-      return -1;
-    }
-    if (k == 0) break;
-    got += k;
-  }
-  return got;
-}
-
-bool is_blank(unsigned char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
-
-/* columns [a, a + width) of the line without the blanks around them */
-void columns(const std::string& s, size_t a, size_t width, const char** t, int* len) {
-  size_t lo = std::min(a, s.size()), hi = std::min(a + width, s.size());
-  while (lo < hi && is_blank((unsigned char)s[lo])) lo++;
-  while (hi > lo && is_blank((unsigned char)s[hi - 1])) hi--;
-  *t = s.data() + lo;
-  *len = (int)(hi - lo);
-}
-
-/* one E field: the canonical field with its pad restored, else the E-less
- * exponent repaired, D or d as the exponent letter, and strtod of all of it */
-bool double_field(const char* t, int len, double* v) {
-  char f[24];
-  if (len < 1 || len > 14) return false;
-  if (len == 14 && t[0] == '-') {
-    memcpy(f, t, 14);
-    if (c2d_scan_e14_7(cens_tab(), f, v) >= 0) return true;
-  } else if (len == 13) {
-    f[0] = ' ';
-    memcpy(f + 1, t, 13);
-    if (c2d_scan_e14_7(cens_tab(), f, v) >= 0) return true;
-  }
-  int n = 0, last_sign = -1;
-  bool has_e = false;
-  for (int i = 0; i < len; i++) {
-    char c = t[i];
-    if (c == 'D' || c == 'd') c = 'E';
-    if (c == 'E' || c == 'e') has_e = true;
-    if ((c == '+' || c == '-') && i > 0) last_sign = n;
-    f[n++] = c;
-  }
-  if (!has_e && last_sign > 0) {
-    memmove(f + last_sign + 1, f + last_sign, (size_t)(n - last_sign));
-    f[last_sign] = 'E';
-    n++;
-  }
-  f[n] = 0;
-  char* end = nullptr;
-  *v = strtod(f, &end);
-  return end == f + n;
-}
-
-/* one I5 field: an optional sign and digits */
-bool int_field(const char* t, int len, int32_t* v) {
-  int i = 0;
-  bool neg = false;
-  if (len > 0 && (t[0] == '-' || t[0] == '+')) { neg = t[0] == '-'; i = 1; }
-  if (i >= len || len > 10) return false;
-  int64_t a = 0;
-  for (; i < len; i++) {
-    if (t[i] < '0' || t[i] > '9') return false;
-    a = a * 10 + (t[i] - '0');
-  }
-  *v = (int32_t)(neg ? -a : a);
-  return true;
-}
-
-struct HostParse {
-  std::vector<double> d6;
-  std::vector<int32_t> i5;
-  std::vector<int64_t> seed;
-  std::vector<uint64_t> keys;
-  int64_t cap;          /* records per delivery */
-  int kfd;              /* the keys file, or -1 */
-  c2d_cens_sink sink;
-  void* user;
-  int64_t* delivered;
-  c2d_cens_times* T;
-  const char* path;
-  int flush(char* err, size_t errlen) {
-    const int64_t n = (int64_t)seed.size();
-    if (n == 0) return C2D_OK;
-    keys.resize((size_t)n);
-    if (kfd >= 0) {
-      int64_t got = 0;
-      while (got < 8 * n) {
-        const ssize_t k = pread(kfd, (unsigned char*)keys.data() + got, (size_t)(8 * n - got),
-                                (off_t)(8 * *delivered + got));
-        if (k < 0 && errno == EINTR) continue;
-        if (k <= 0) break;
-        got += k;
-      }
-      if (got != 8 * n)
-        return efail(err, errlen, C2D_E_IO, "census: '%s.keys' holds fewer keys than '%s' has records", path, path);
-    } else {
-      for (int64_t r = 0; r < n; r++) keys[(size_t)r] = c2d_cens_derive_key(seed[(size_t)r], *delivered + r);
-    }
-    const int rc = sink ? sink(user, d6.data(), i5.data(), keys.data(), n, 0) : C2D_OK;
-    if (rc) return rc;
-    *delivered += n;
-    T->host_records += n;
-    d6.clear();
-    i5.clear();
-    seed.clear();
-    return C2D_OK;
-  }
-};
-
-/* the host parser from byte `off` (the start of a record) to the end of the file */
-int host_parse(int fd, int kfd, int64_t off, int64_t chunk, c2d_cens_sink sink, void* user, int64_t* delivered,
-               c2d_cens_times* T, const char* path, char* err, size_t errlen) {
-  if (lseek(fd, (off_t)off, SEEK_SET) < 0)
-    return efail(err, errlen, C2D_E_IO, "census: cannot seek in '%s': %s", path, strerror(errno));
-  HostParse H{{}, {}, {}, {}, chunk, kfd, sink, user, delivered, T, path};
-  std::vector<unsigned char> buf((size_t)1 << 20);
-  std::string line, first;
-  int64_t pos = off, line_off = off, first_off = 0;
-  bool have_first = false;
-  int rc = C2D_OK;
-  for (bool eof = false; !eof && !rc;) {
-    const int64_t got = read_full(fd, buf.data(), (int64_t)buf.size());
-    if (got < 0) return efail(err, errlen, C2D_E_IO, "census: cannot read '%s': %s", path, strerror(errno));
-    eof = got < (int64_t)buf.size();
-    for (int64_t i = 0; i <= got && !rc; i++) {
-      const bool end_of_text = i == got;
-      if (end_of_text && !eof) break;
-      if (!end_of_text && buf[(size_t)i] != '\n') {
-        if (line.empty()) line_off = pos + i;
-        if (line.size() < 4096) line.push_back((char)buf[(size_t)i]);
-        continue;
-      }
-      /* a line ends here (or the text does: a missing final newline) */
-      bool blank = true;
-      for (char c : line) blank = blank && is_blank((unsigned char)c);
-      if (blank) { line.clear(); continue; }
-      if (!have_first) {
-        first.swap(line);
-        first_off = line_off;
-        have_first = true;
-        line.clear();
-        continue;
-      }
-      have_first = false;
-      const char* t;
-      int len;
-      for (int c = 0; c < 6 && !rc; c++) {
-        double v = 0.0;
-        columns(first, 14 * (size_t)c, 14, &t, &len);
-        if (!double_field(t, len, &v))
-          rc = efail(err, errlen, C2D_E_IO, "census: '%s': field '%.*s' at byte offset %lld is not a number", path, len,
-                     t, (long long)(first_off + 14 * c));
-        H.d6.push_back(v);
-      }
-      for (int c = 0; c < 6 && !rc; c++) {
-        int32_t v = 0;
-        columns(line, 5 * (size_t)c, 5, &t, &len);
-        if (!int_field(t, len, &v))
-          rc = efail(err, errlen, C2D_E_IO, "census: '%s': field '%.*s' at byte offset %lld is not an integer", path,
-                     len, t, (long long)(line_off + 5 * c));
-        if (c < 5) H.i5.push_back(v); else H.seed.push_back(v);
-      }
-      line.clear();
-      if (!rc && (int64_t)H.seed.size() >= H.cap) rc = H.flush(err, errlen);
-    }
-    pos += got;
-  }
-  if (!rc && have_first)
-    rc = efail(err, errlen, C2D_E_IO, "census: '%s': an odd number of lines: the record at byte offset %lld has no "
-               "integer line", path, (long long)first_off);
-  if (!rc) rc = H.flush(err, errlen);
-  return rc;
-}
-
-/* chunk of `n` records in pin[b] (and kpin[b]) -> device text -> plain records */
-int enqueue(c2d_cens_file* r, hipStream_t stream, int b, int64_t n, int64_t rec_base, bool have_keys, char* err,
-            size_t errlen) {
-  CFCHK(hipMemcpyAsync(r->text_d, r->pin[b], (size_t)n * C2D_CENS_RECORD, hipMemcpyHostToDevice, stream));
-  if (have_keys)
-    CFCHK(hipMemcpyAsync(r->keys_d, r->kpin[b], (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  const char* e = getenv("C2D_SCAN_SELFTEST_EXACT");
-  CFCHK(hipEventRecord(r->ka[b], stream));
-  hipLaunchKernelGGL(c2d_censparse_kernel, dim3((unsigned)((n + C2D_CENS_BLOCK - 1) / C2D_CENS_BLOCK)),
-                     dim3(C2D_CENS_BLOCK), 0, stream, r->text_d, n, rec_base, r->tab_d, r->d6_d, r->i5_d, r->keys_d,
-                     have_keys ? 0 : 1, r->stat_d, e && e[0] == '1');
-  CFCHK(hipGetLastError());
-  CFCHK(hipEventRecord(r->kb[b], stream));
-  CFCHK(hipMemcpyAsync(&r->stat_h[b], r->stat_d, sizeof(CensStat), hipMemcpyDeviceToHost, stream));
-  CFCHK(hipEventRecord(r->done[b], stream));
-  return C2D_OK;
-}
-
-int read_chunks(c2d_cens_file* r, hipStream_t stream, int fd, int kfd, const char* path, int64_t chunk,
-                c2d_cens_sink sink, void* user, int64_t* delivered, c2d_cens_times* T, char* err, size_t errlen) {
-  const int64_t chunk_bytes = chunk * C2D_CENS_RECORD;
-  r->stat_h[2].nonfinite = 0ull;
-  r->stat_h[2].first_bad = ~0ull;
-  CFCHK(hipMemcpyAsync(r->stat_d, &r->stat_h[2], sizeof(CensStat), hipMemcpyHostToDevice, stream));
-  bool eof = false;
-  int64_t prev_n = 0, prev_base = 0;   /* the chunk in flight: its records and its byte offset */
-  int64_t nkeys[2] = {0, 0};           /* keys read beside each chunk (fewer than its 116-byte slots
-                                          where the text is not canonical, or the keys file is short) */
-  int prev_b = 0;
-  int64_t host_off = -1;               /* where the host parser takes over */
-  for (int64_t k = 0;; k++) {
-    const int b = (int)(k & 1);
-    int64_t cur_n = 0;
-    if (!eof) {   /* chunk k into the pinned buffers b while chunk k - 1 is copied and parsed */
-      const double t0 = now_ms();
-      const int64_t got = read_full(fd, r->pin[b], chunk_bytes);
-      if (got < 0) return efail(err, errlen, C2D_E_IO, "census: cannot read '%s': %s", path, strerror(errno));
-      cur_n = got / C2D_CENS_RECORD;
-      eof = got < chunk_bytes;
-      if (got % C2D_CENS_RECORD) host_off = k * chunk_bytes + cur_n * C2D_CENS_RECORD;   /* a tail shorter than a record */
-      if (kfd >= 0 && cur_n > 0) {
-        const int64_t kgot = read_full(kfd, r->kpin[b], 8 * cur_n);
-        if (kgot < 0) return efail(err, errlen, C2D_E_IO, "census: cannot read '%s.keys': %s", path, strerror(errno));
-        nkeys[b] = kgot / 8;
-      }
-      T->io_ms += now_ms() - t0;
-    }
-    if (prev_n > 0) {   /* chunk k - 1 to the sink */
-      const double t0 = now_ms();
-      CFCHK(hipEventSynchronize(r->done[prev_b]));
-      T->wait_ms += now_ms() - t0;
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, r->ka[prev_b], r->kb[prev_b]);
-      T->kernel_ms += ms;
-      T->chunks++;
-      const unsigned long long fb = r->stat_h[prev_b].first_bad;
-      const int64_t good = fb < (unsigned long long)prev_n ? (int64_t)fb : prev_n;
-      if (kfd >= 0 && good > nkeys[prev_b])
-        return efail(err, errlen, C2D_E_IO, "census: '%s.keys' holds fewer keys than '%s' has records", path, path);
-      if (good > 0 && sink) {
-        const int rc = sink(user, r->d6_d, r->i5_d, r->keys_d, good, 1);
-        if (rc) return rc;
-      }
-      *delivered += good;
-      T->device_records += good;
-      if (good < prev_n) {   /* not canonical from here on: the host parser's */
-        host_off = prev_base + good * C2D_CENS_RECORD;
-        break;
-      }
-      prev_n = 0;
-    }
-    if (cur_n > 0) {
-      const int rc = enqueue(r, stream, b, cur_n, k * chunk, kfd >= 0, err, errlen);
-      if (rc) return rc;
-      prev_n = cur_n;
-      prev_b = b;
-      prev_base = k * chunk_bytes;
-    }
-    if (eof && prev_n == 0) break;
-  }
-  if (host_off >= 0) return host_parse(fd, kfd, host_off, chunk, sink, user, delivered, T, path, err, errlen);
-  return C2D_OK;
-}
-
-}  // namespace
 
 extern "C" int c2d_censtext_read(c2d_cens_file** pr, int device, hipStream_t stream, const char* path,
                                  c2d_cens_sink sink, void* user, int64_t* n_records, c2d_cens_times* times,
@@ -739,17 +379,51 @@ extern "C" int c2d_censtext_read(c2d_cens_file** pr, int device, hipStream_t str
     (void)close(fd);
     return efail(err, errlen, C2D_E_IO, "census: cannot open '%s': %s", kpath.c_str(), strerror(e));
   }
-  int64_t chunk = chunk_records();
+  int64_t chunk = chunk_env("C2D_CENSTEXT_CHUNK", 1ll << 24);
   struct stat sb;
   if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode))   /* a small file needs small buffers */
     chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (int64_t)sb.st_size / C2D_CENS_RECORD));
-  if (!*pr) {
-    *pr = new c2d_cens_file;
-    (*pr)->device = device;
-  }
-  int rc = ensure(*pr, chunk, err, errlen);
+  int rc = ensure(pr, device, chunk, err, errlen);
   if (!rc) {
-    rc = read_chunks(*pr, stream, fd, kfd, path, chunk, sink, user, &delivered, &T, err, errlen);
+    c2d_cens_file* r = *pr;
+    TextStage<CensStat>& st = r->st;
+    int64_t nkeys[2] = {0, 0};   /* keys read beside each chunk (fewer than its 116-byte slots where the
+                                    text is not canonical, or the keys file is short) */
+    const char* e = getenv("C2D_SCAN_SELFTEST_EXACT");
+    const int force_exact = e && e[0] == '1';
+    auto side = [&](int b, int64_t n) {
+      if (kfd < 0) return C2D_OK;
+      const int64_t kgot = read_full(kfd, r->kpin[b], 8 * n);
+      if (kgot < 0) return efail(err, errlen, C2D_E_IO, "census: cannot read '%s.keys': %s", path, strerror(errno));
+      nkeys[b] = kgot / 8;
+      return C2D_OK;
+    };
+    /* chunk k of n records (its keys in kpin[b]): device text -> plain records */
+    auto enqueue = [&](int b, int64_t n, int64_t k) {
+      if (kfd >= 0)
+        C2D_TXCHK(hipMemcpyAsync(r->keys_d, r->kpin[b], (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+      return st.timed(stream, b, [&] {
+        hipLaunchKernelGGL(c2d_censparse_kernel, dim3((unsigned)((n + C2D_CENS_BLOCK - 1) / C2D_CENS_BLOCK)),
+                           dim3(C2D_CENS_BLOCK), 0, stream, st.text_d, n, k * chunk, st.tab_d, r->d6_d, r->i5_d,
+                           r->keys_d, kfd >= 0 ? 0 : 1, st.stat_d, force_exact);
+      }, err, errlen);
+    };
+    auto deliver = [&](int b, int64_t good) {
+      if (kfd >= 0 && good > nkeys[b])
+        return efail(err, errlen, C2D_E_IO, "census: '%s.keys' holds fewer keys than '%s' has records", path, path);
+      if (good > 0 && sink) {
+        const int rc = sink(user, r->d6_d, r->i5_d, r->keys_d, good, 1);
+        if (rc) return rc;
+      }
+      delivered += good;
+      T.device_records += good;
+      return C2D_OK;
+    };
+    auto host = [&](int64_t off) {
+      return cens_host_parse(fd, kfd, off, chunk, sink, user, &delivered, &T, path, err, errlen);
+    };
+    rc = read_chunks(st, stream, fd, "census", path, C2D_CENS_RECORD, chunk, CENS_STAT0, &T, side, enqueue, deliver,
+                     host, err, errlen);
     if (rc) (void)hipStreamSynchronize(stream);   /* nothing in flight out of the staging buffers */
   }
   if (!rc && kfd >= 0 && fstat(kfd, &sb) == 0 && (int64_t)sb.st_size != 8 * delivered)
@@ -764,21 +438,10 @@ extern "C" int c2d_censtext_read(c2d_cens_file** pr, int device, hipStream_t str
 
 extern "C" void c2d_censtext_free(c2d_cens_file* w) {
   if (!w) return;
-  (void)hipSetDevice(w->device);
-  if (w->tab_d) (void)hipFree(w->tab_d);
-  if (w->stat_d) (void)hipFree(w->stat_d);
-  if (w->stat_h) (void)hipHostFree(w->stat_h);
-  if (w->text_d) (void)hipFree(w->text_d);
-  if (w->d6_d) (void)hipFree(w->d6_d);
-  if (w->i5_d) (void)hipFree(w->i5_d);
-  if (w->keys_d) (void)hipFree(w->keys_d);
-  for (int b = 0; b < 2; b++) {
-    if (w->pin[b]) (void)hipHostFree(w->pin[b]);
-    if (w->kpin[b]) (void)hipHostFree(w->kpin[b]);
-    if (w->done[b]) (void)hipEventDestroy(w->done[b]);
-    if (w->ka[b]) (void)hipEventDestroy(w->ka[b]);
-    if (w->kb[b]) (void)hipEventDestroy(w->kb[b]);
+  (void)hipSetDevice(w->st.device);
+  w->st.release();
+  free_records(w);
+  for (int b = 0; b < 2; b++)
     if (w->kc[b]) (void)hipEventDestroy(w->kc[b]);
-  }
   delete w;
 }

@@ -19,18 +19,7 @@
  */
 #include "c2d_evtext.hpp"
 
-#include <errno.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <chrono>
-#include <mutex>
-
-#include "../../include/compton2d.h"
-#include "c2d_fmt.h"
+#include "c2d_textio.hpp"
 
 namespace c2d {
 
@@ -164,57 +153,19 @@ __global__ void c2d_fmt_selftest_kernel(const c2d_fmt_tab* __restrict__ tab, con
   for (int b = 0; b < 6; b++) o[8 + b] = (char)(w1 >> (8 * b));
 }
 
-/* the powers-of-ten table, built once per process */
-static const c2d_fmt_tab* host_tab() {
-  static c2d_fmt_tab tab;
-  static std::once_flag once;
-  std::call_once(once, [] { c2d_fmt_tab_build(&tab); });
-  return &tab;
-}
-
 }  // namespace c2d
 
 using namespace c2d;
 
 struct c2d_evt_writer {
-  int device = 0;
-  c2d_fmt_tab* tab_d = nullptr;
-  EvtStat* stat_d = nullptr;
-  EvtStat* stat_h = nullptr;          /* pinned: [2] */
-  char* text_d = nullptr;             /* cap events of text */
-  char* pin[2] = {nullptr, nullptr};  /* pinned host staging, cap events each */
-  int64_t cap = 0;
+  TextStage<EvtStat> st;              /* the text buffer has no pad: the kernel stores the exact bytes */
   double* stage_d = nullptr;          /* host-supplied events, one chunk */
   int64_t stage_cap = 0;
-  hipEvent_t done[2] = {nullptr, nullptr}, ka[2] = {nullptr, nullptr}, kb[2] = {nullptr, nullptr};
 };
 
 namespace {
 
-int efail(char* err, size_t n, int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  if (err && n) vsnprintf(err, n, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define EVCHK(x)                                                                              \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess)                                                                     \
-      return efail(err, errlen, C2D_E_HIP, "%s:%d %s: %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); \
-  } while (0)
-
-/* events per chunk: C2D_EVTEXT_CHUNK, read at every call (a test knob) */
-int64_t chunk_events() {
-  const char* e = getenv("C2D_EVTEXT_CHUNK");
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v >= 1) return (int64_t)v;
-  }
-  return (int64_t)1 << 20;
-}
+constexpr EvtStat EVT_STAT0 = {0ull, ~0ull, 0ull, 0ull};   /* nothing met yet */
 
 /* the segments of records [c0, c1) of the concatenation */
 void chunk_segments(const double* const* seg, const int64_t* cnt, int nseg, int64_t c0, int64_t c1, bool rec_global,
@@ -237,33 +188,13 @@ void chunk_segments(const double* const* seg, const int64_t* cnt, int nseg, int6
 }
 
 int ensure(c2d_evt_writer* w, int64_t events, int64_t stage_events, char* err, size_t errlen) {
-  if (!w->tab_d) {
-    EVCHK(hipMalloc((void**)&w->tab_d, sizeof(c2d_fmt_tab)));
-    EVCHK(hipMemcpy(w->tab_d, host_tab(), sizeof(c2d_fmt_tab), hipMemcpyHostToDevice));
-    EVCHK(hipMalloc((void**)&w->stat_d, sizeof(EvtStat)));
-    EVCHK(hipHostMalloc((void**)&w->stat_h, 2 * sizeof(EvtStat), hipHostMallocDefault));
-    for (int b = 0; b < 2; b++) {
-      EVCHK(hipEventCreateWithFlags(&w->done[b], hipEventDisableTiming));
-      EVCHK(hipEventCreate(&w->ka[b]));
-      EVCHK(hipEventCreate(&w->kb[b]));
-    }
-  }
-  if (events > w->cap) {
-    if (w->text_d) (void)hipFree(w->text_d);
-    for (int b = 0; b < 2; b++)
-      if (w->pin[b]) (void)hipHostFree(w->pin[b]);
-    w->text_d = w->pin[0] = w->pin[1] = nullptr;
-    w->cap = 0;
-    const size_t bytes = (size_t)events * C2D_EVT_RECORD;
-    EVCHK(hipMalloc((void**)&w->text_d, bytes));
-    for (int b = 0; b < 2; b++) EVCHK(hipHostMalloc((void**)&w->pin[b], bytes, hipHostMallocDefault));
-    w->cap = events;
-  }
+  { const int rc = w->st.ensure(events, C2D_EVT_RECORD, false, [](int64_t) { return C2D_OK; }, err, errlen);
+    if (rc) return rc; }
   if (stage_events > w->stage_cap) {
     if (w->stage_d) (void)hipFree(w->stage_d);
     w->stage_d = nullptr;
     w->stage_cap = 0;
-    EVCHK(hipMalloc((void**)&w->stage_d, (size_t)stage_events * 7 * sizeof(double)));
+    C2D_TXCHK(hipMalloc((void**)&w->stage_d, (size_t)stage_events * 7 * sizeof(double)));
     w->stage_cap = stage_events;
   }
   return C2D_OK;
@@ -275,63 +206,33 @@ int nonfinite_error(unsigned long long count, unsigned long long first, char* er
                "the file was not touched", count, first / 7ull + 1ull, first % 7ull + 1ull);
 }
 
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 /* the chunks of [0, n) through the two pinned buffers into f */
-int write_chunks(c2d_evt_writer* w, hipStream_t stream, const double* const* seg, const int64_t* cnt, int nseg,
+int write_events(c2d_evt_writer* w, hipStream_t stream, const double* const* seg, const int64_t* cnt, int nseg,
                  int on_device, int64_t n, int64_t chunk, FILE* f, const char* path, c2d_evt_times* T, char* err,
                  size_t errlen) {
-  const int64_t nchunks = (n + chunk - 1) / chunk;
-  EvtStat init = {0ull, ~0ull, 0ull, 0ull};
-  EVCHK(hipMemcpyAsync(w->stat_d, &init, sizeof init, hipMemcpyHostToDevice, stream));
-  EVCHK(hipStreamSynchronize(stream));   /* `init` is on this stack */
-  for (int64_t k = 0; k <= nchunks; k++) {
-    if (k < nchunks) {   /* chunk k: format, copy to pinned buffer k % 2 */
-      const int b = (int)(k & 1);
-      const int64_t c0 = k * chunk, c1 = std::min(n, c0 + chunk);
-      EvtSegs S;
-      if (on_device) {
-        chunk_segments(seg, cnt, nseg, c0, c1, false, &S);
-      } else {
-        EVCHK(hipMemcpyAsync(w->stage_d, seg[0] + c0 * 7, (size_t)(c1 - c0) * 7 * sizeof(double),
-                             hipMemcpyHostToDevice, stream));
-        const double* sd = w->stage_d;
-        const int64_t m = c1 - c0;
-        chunk_segments(&sd, &m, 1, 0, m, false, &S);
-      }
-      EVCHK(hipEventRecord(w->ka[b], stream));
+  TextStage<EvtStat>& st = w->st;
+  auto produce = [&](int b, int64_t c0, int64_t m) {
+    EvtSegs S;
+    if (on_device) {
+      chunk_segments(seg, cnt, nseg, c0, c0 + m, false, &S);
+    } else {
+      C2D_TXCHK(hipMemcpyAsync(w->stage_d, seg[0] + c0 * 7, (size_t)m * 7 * sizeof(double), hipMemcpyHostToDevice,
+                               stream));
+      const double* sd = w->stage_d;
+      chunk_segments(&sd, &m, 1, 0, m, false, &S);
+    }
+    return st.timed(stream, b, [&] {
       hipLaunchKernelGGL(c2d_evtext_kernel, dim3((unsigned)S.blk0[S.nseg]), dim3(C2D_EVT_BLOCK), 0, stream, S,
-                         w->tab_d, w->text_d, w->stat_d);
-      EVCHK(hipGetLastError());
-      EVCHK(hipEventRecord(w->kb[b], stream));
-      EVCHK(hipMemcpyAsync(w->pin[b], w->text_d, (size_t)(c1 - c0) * C2D_EVT_RECORD, hipMemcpyDeviceToHost, stream));
-      EVCHK(hipMemcpyAsync(&w->stat_h[b], w->stat_d, sizeof(EvtStat), hipMemcpyDeviceToHost, stream));
-      EVCHK(hipEventRecord(w->done[b], stream));
-    }
-    if (k > 0) {   /* chunk k - 1: to the file while chunk k is formatted and copied */
-      const int b = (int)((k - 1) & 1);
-      const int64_t c0 = (k - 1) * chunk, c1 = std::min(n, c0 + chunk);
-      const double t0 = now_ms();
-      EVCHK(hipEventSynchronize(w->done[b]));
-      const double t1 = now_ms();
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, w->ka[b], w->kb[b]);
-      T->kernel_ms += ms;
-      T->wait_ms += t1 - t0;
-      T->ambiguous = (int64_t)w->stat_h[b].ambiguous;
-      T->multilimb = (int64_t)w->stat_h[b].multilimb;
-      T->chunks++;
-      if (w->stat_h[b].nonfinite)   /* the scan found none: the events changed under the call */
-        return efail(err, errlen, C2D_E_STATE, "events: a non-finite value appeared while '%s' was written", path);
-      const size_t bytes = (size_t)(c1 - c0) * C2D_EVT_RECORD;
-      if (fwrite(w->pin[b], 1, bytes, f) != bytes)
-        return efail(err, errlen, C2D_E_IO, "events: cannot write '%s': %s", path, strerror(errno));
-      T->io_ms += now_ms() - t1;
-    }
-  }
-  return C2D_OK;
+                         st.tab_d, (char*)st.text_d, st.stat_d);
+    }, err, errlen);
+  };
+  auto counts = [&](int b) {
+    T->ambiguous = (int64_t)st.stat_h[b].ambiguous;
+    T->multilimb = (int64_t)st.stat_h[b].multilimb;
+  };
+  auto nothing = [](int, int64_t) { return C2D_OK; };
+  return write_chunks(st, stream, f, "events", path, C2D_EVT_RECORD, n, chunk, EVT_STAT0, T, produce, nothing, counts,
+                      nothing, err, errlen);
 }
 
 }  // namespace
@@ -347,34 +248,35 @@ extern "C" int c2d_evtext_write(c2d_evt_writer** pw, int device, hipStream_t str
   if (n > 0) {
     if (!*pw) {
       *pw = new c2d_evt_writer;
-      (*pw)->device = device;
+      (*pw)->st.device = device;
     }
     c2d_evt_writer* w = *pw;
-    const int64_t chunk = chunk_events();
+    TextStage<EvtStat>& st = w->st;
+    const int64_t chunk = chunk_env("C2D_EVTEXT_CHUNK", 0);
     const int64_t m = std::min(chunk, n);
     { const int rc = ensure(w, m, on_device ? 0 : m, err, errlen); if (rc) return rc; }
     /* non-finite values first: the file is opened only once there is none */
     if (on_device) {
-      EvtStat init = {0ull, ~0ull, 0ull, 0ull};
+      EvtStat init = EVT_STAT0;
       EvtSegs S;
       int64_t done = 0;
-      EVCHK(hipMemcpyAsync(w->stat_d, &init, sizeof init, hipMemcpyHostToDevice, stream));
-      EVCHK(hipEventRecord(w->ka[0], stream));
+      C2D_TXCHK(hipMemcpyAsync(st.stat_d, &init, sizeof init, hipMemcpyHostToDevice, stream));
+      C2D_TXCHK(hipEventRecord(st.ka[0], stream));
       while (done < n) {   /* launches of at most 2^30 events (the workgroup index is an int32) */
         const int64_t c1 = std::min(n, done + ((int64_t)1 << 30));
         chunk_segments(seg, cnt, nseg, done, c1, true, &S);
         hipLaunchKernelGGL(c2d_evscan_kernel, dim3((unsigned)S.blk0[S.nseg]), dim3(C2D_EVT_BLOCK), 0, stream, S,
-                           w->stat_d);
-        EVCHK(hipGetLastError());
+                           st.stat_d);
+        C2D_TXCHK(hipGetLastError());
         done = c1;
       }
-      EVCHK(hipEventRecord(w->kb[0], stream));
-      EVCHK(hipMemcpyAsync(&w->stat_h[0], w->stat_d, sizeof(EvtStat), hipMemcpyDeviceToHost, stream));
-      EVCHK(hipStreamSynchronize(stream));
+      C2D_TXCHK(hipEventRecord(st.kb[0], stream));
+      C2D_TXCHK(hipMemcpyAsync(&st.stat_h[0], st.stat_d, sizeof(EvtStat), hipMemcpyDeviceToHost, stream));
+      C2D_TXCHK(hipStreamSynchronize(stream));
       float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, w->ka[0], w->kb[0]);
+      (void)hipEventElapsedTime(&ms, st.ka[0], st.kb[0]);
       T.scan_ms = ms;
-      if (w->stat_h[0].nonfinite) return nonfinite_error(w->stat_h[0].nonfinite, w->stat_h[0].first_bad, err, errlen);
+      if (st.stat_h[0].nonfinite) return nonfinite_error(st.stat_h[0].nonfinite, st.stat_h[0].first_bad, err, errlen);
     } else {
       const double t0 = now_ms();
       const uint64_t* u = reinterpret_cast<const uint64_t*>(seg[0]);
@@ -387,7 +289,7 @@ extern "C" int c2d_evtext_write(c2d_evt_writer** pw, int device, hipStream_t str
     FILE* f = fopen(path, append ? "ab" : "wb");
     if (!f) return efail(err, errlen, C2D_E_IO, "events: cannot open '%s': %s", path, strerror(errno));
     setvbuf(f, nullptr, _IONBF, 0);   /* the chunks are the buffer */
-    int rc = write_chunks(w, stream, seg, cnt, nseg, on_device, n, chunk, f, path, &T, err, errlen);
+    int rc = write_events(w, stream, seg, cnt, nseg, on_device, n, chunk, f, path, &T, err, errlen);
     if (rc) (void)hipStreamSynchronize(stream);   /* nothing in flight into the staging buffers */
     if (fclose(f) != 0 && !rc) rc = efail(err, errlen, C2D_E_IO, "events: cannot close '%s': %s", path, strerror(errno));
     if (rc) return rc;
@@ -403,18 +305,9 @@ extern "C" int c2d_evtext_write(c2d_evt_writer** pw, int device, hipStream_t str
 
 extern "C" void c2d_evtext_free(c2d_evt_writer* w) {
   if (!w) return;
-  (void)hipSetDevice(w->device);
-  if (w->tab_d) (void)hipFree(w->tab_d);
-  if (w->stat_d) (void)hipFree(w->stat_d);
-  if (w->stat_h) (void)hipHostFree(w->stat_h);
-  if (w->text_d) (void)hipFree(w->text_d);
+  (void)hipSetDevice(w->st.device);
+  w->st.release();
   if (w->stage_d) (void)hipFree(w->stage_d);
-  for (int b = 0; b < 2; b++) {
-    if (w->pin[b]) (void)hipHostFree(w->pin[b]);
-    if (w->done[b]) (void)hipEventDestroy(w->done[b]);
-    if (w->ka[b]) (void)hipEventDestroy(w->ka[b]);
-    if (w->kb[b]) (void)hipEventDestroy(w->kb[b]);
-  }
   delete w;
 }
 
@@ -431,7 +324,7 @@ extern "C" int c2d_selftest_fmt(int device, const double* x_host, int64_t n, cha
   if (hipMalloc((void**)&tab, sizeof(c2d_fmt_tab)) != hipSuccess || hipMalloc((void**)&x, n * sizeof(double)) != hipSuccess ||
       hipMalloc((void**)&out, (size_t)n * 14) != hipSuccess || hipMalloc((void**)&st, sizeof(EvtStat)) != hipSuccess)
     rc = C2D_E_HIP;
-  if (!rc && (hipMemcpy(tab, host_tab(), sizeof(c2d_fmt_tab), hipMemcpyHostToDevice) != hipSuccess ||
+  if (!rc && (hipMemcpy(tab, fmt_tab(), sizeof(c2d_fmt_tab), hipMemcpyHostToDevice) != hipSuccess ||
               hipMemcpy(x, x_host, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
               hipMemcpy(st, &h, sizeof h, hipMemcpyHostToDevice) != hipSuccess ||
               hipMemset(out, '#', (size_t)n * 14) != hipSuccess))
