@@ -656,3 +656,21 @@ class VemCall:
               for k in tabs]
         m2 = [MArray2(r[k].ctypes.data_as(PD), nr, 1) for k in ("B_field", "Eloss_sy", "Eloss_cy", "Eloss_th", "Eloss_tot")]
         self.sout = VemOut(*m3, *m2, r["E_ph"].ctypes.data_as(PD))
+
+
+# ---------------------------------------------------------------------------
+# Checkpoints (c2d_checkpoint_*; the format in compton2d_amd/checkpoint.py)
+# ---------------------------------------------------------------------------
+CKPT_VERSION = 1
+CKPT_HAS_KAPPA, CKPT_HAS_ELECTRONS = 1, 2      # sections
+CKPT_APPEND, CKPT_CENSUS_ONLY = 1, 2           # c2d_checkpoint_read flags
+
+
+class CkptInfo(C.Structure):
+    """c2d_ckpt_info: a checkpoint's header as c2d_checkpoint_info reports it."""
+    _fields_ = [
+        ("version", _i32), ("nz", _i32), ("nr", _i32), ("nmu", _i32),
+        ("encoded", _i32), ("rank", _i32), ("world", _i32), ("ncycle", _i32),
+        ("sections", _i32), ("fp_auto_known", _i32), ("fp_auto_exact", _i32), ("reserved", _i32),
+        ("grid_digest", C.c_uint64), ("seed", C.c_uint64), ("time", _d), ("dt", _d),
+        ("n_records", _i64), ("chunk", _i64), ("user_bytes", _i64), ("file_bytes", _i64)]

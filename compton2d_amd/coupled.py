@@ -180,3 +180,51 @@ class CoupledRun:
         if self._electrons_on_device():
             return self.eng.electron_state()
         return self.state["f_nt"], self.state["Pnt"]
+
+    # -- checkpoints ---------------------------------------------------------
+    def save(self, path) -> int:
+        """Save the run between two steps (Engine.checkpoint_write): the
+        context's census, kappa_prev, device electrons and FP flags, and as
+        the user blob an .npz (no pickling) of the step number, ecens_prev,
+        the zone scalars of `state` (f_nt / Pnt too while they live on the
+        host) and the workload's nst, dt and seed.  Returns the census
+        records written.  Observer accumulations are not part of it."""
+        import io
+        import zipfile
+        on_dev = self._electrons_on_device()
+        blob = {"n": np.int64(self.n), "ecens_prev": self.ecens_prev,
+                "wl_nst": np.asarray(self.wl.nst), "wl_dt": np.float64(self.wl.dt),
+                "wl_seed": np.uint64(self.wl.grid.seed), "device_resident": np.int64(self.device_resident)}
+        for k, v in self.state.items():
+            if on_dev and k in ("f_nt", "Pnt"):
+                continue
+            blob["state_" + k] = np.asarray(v)
+        # an .npz with fixed member dates: the same state gives the same bytes
+        buf = io.BytesIO()
+        with zipfile.ZipFile(buf, "w", zipfile.ZIP_STORED) as z:
+            for k, v in blob.items():
+                member = io.BytesIO()
+                np.lib.format.write_array(member, np.asanyarray(v), allow_pickle=False)
+                z.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), member.getvalue())
+        return self.eng.checkpoint_write(path, buf.getvalue())
+
+    @classmethod
+    def restore(cls, eng: Engine, wl: CoupledWorkload, path, **kw) -> "CoupledRun":
+        """A run on `eng` (a fresh context of the workload's grid) that
+        carries on where save() stopped: step() runs step n.  kw: the
+        constructor's arguments; device_resident must be the saved run's."""
+        import io
+        run = cls(eng, wl, **kw)
+        _, user = eng.checkpoint_read(path)
+        with np.load(io.BytesIO(user), allow_pickle=False) as z:
+            if (not np.array_equal(z["wl_nst"], np.asarray(wl.nst)) or float(z["wl_dt"]) != float(wl.dt)
+                    or int(z["wl_seed"]) != int(wl.grid.seed)):
+                raise ValueError("checkpoint '%s' was saved by another workload (nst, dt or seed differ)" % path)
+            if bool(z["device_resident"]) != bool(run.device_resident):
+                raise ValueError("checkpoint '%s' was saved with device_resident=%s" % (path, bool(z["device_resident"])))
+            run.n = int(z["n"])
+            run.ecens_prev = np.array(z["ecens_prev"], copy=True)
+            for k in z.files:
+                if k.startswith("state_"):
+                    run.state[k[len("state_"):]] = np.array(z[k], copy=True)
+        return run

@@ -223,6 +223,10 @@ __device__ __forceinline__ void cst4_nt(c2d_u4* p, uint32_t jk, uint32_t bins, u
 __device__ __forceinline__ c2d_u4 cld4_nt(const c2d_u4* p) {
   return __builtin_nontemporal_load((const C2D_GLOBAL c2d_u4*)p);
 }
+/* census record i -> its slot (chunked: through the chunk list) */
+__device__ __forceinline__ int64_t cens_slot(const int32_t* clist, int64_t i) {
+  return clist ? ((int64_t)clist[i >> C2D_CCHUNK_LOG] << C2D_CCHUNK_LOG) + (i & (C2D_CCHUNK - 1)) : i;
+}
 /* a record's bins word alone (compaction scans, dead marks) */
 __device__ __forceinline__ uint32_t cens_bins(const c2d_u4* tg, int64_t s) {
   return gld(reinterpret_cast<const uint32_t*>(tg + s) + 1);

@@ -111,39 +111,47 @@ struct TextStage {
 };
 
 /*
- * The file `fd` of `record`-byte records to the device, `chunk` records at a
- * time: chunk k is read into pinned buffer k & 1 while chunk k - 1 is copied
- * and parsed; then chunk k - 1 is retired.  `what` names the format in the
- * messages ("events", "census").
+ * The file `fd` of `record`-byte records to the device, a chunk at a time:
+ * chunk k is read into pinned buffer k & 1 while chunk k - 1 is copied and
+ * parsed; then chunk k - 1 is retired.  `what` names the format in the
+ * messages ("events", "census").  A chunk is `head` bytes (the checkpoint's
+ * chunk head; 0 in the text files) and then whole records; offsets count
+ * from where fd stands at the call.
+ *   want(k)           bytes of chunk k, head included; 0: no further chunk
  *   side(b, n)        reads what lies beside the n records of buffer b (inside io_ms)
  *   enqueue(b, n, k)  queues the parse of chunk k, n records, whose text is on the device
  *   deliver(b, good)  hands over the canonical prefix of buffer b's chunk
  *   host(off)         parses from byte `off` to the end of the file on the host
  * The kernels lower Stat::first_bad to the first record that is not canonical.
  */
-template <class Stat, class Times, class Side, class Enqueue, class Deliver, class Host>
-int read_chunks(TextStage<Stat>& r, hipStream_t stream, int fd, const char* what, const char* path, int record,
-                int64_t chunk, const Stat& init, Times* T, Side&& side, Enqueue&& enqueue, Deliver&& deliver,
-                Host&& host, char* err, size_t errlen) {
-  const int64_t chunk_bytes = chunk * record;
+template <class Stat, class Times, class Want, class Side, class Enqueue, class Deliver, class Host>
+int read_chunks_sized(TextStage<Stat>& r, hipStream_t stream, int fd, const char* what, const char* path, int record,
+                      int head, Want&& want, const Stat& init, Times* T, Side&& side, Enqueue&& enqueue,
+                      Deliver&& deliver, Host&& host, char* err, size_t errlen) {
   { const int rc = r.reset(stream, init, err, errlen); if (rc) return rc; }
   bool eof = false;
   int64_t prev_n = 0, prev_base = 0;   /* the chunk in flight: its records and its byte offset */
+  int64_t file_off = 0;                /* bytes taken from fd so far */
   int prev_b = 0;
   int64_t host_off = -1;               /* where the host parser takes over */
   for (int64_t k = 0;; k++) {
     const int b = (int)(k & 1);
     int64_t cur_n = 0;
+    const int64_t cur_base = file_off;
+    const int64_t need = eof ? 0 : want(k);
+    if (need == 0) eof = true;
     if (!eof) {   /* chunk k into pinned buffer b while chunk k - 1 is copied and parsed */
       const double t0 = now_ms();
-      const int64_t got = read_full(fd, r.pin[b], chunk_bytes);
+      const int64_t got = read_full(fd, r.pin[b], need);
       if (got < 0) {
         T->io_ms += now_ms() - t0;
         return efail(err, errlen, C2D_E_IO, "%s: cannot read '%s': %s", what, path, strerror(errno));
       }
-      cur_n = got / record;
-      eof = got < chunk_bytes;
-      if (got % record) host_off = k * chunk_bytes + cur_n * record;   /* a tail shorter than a record */
+      cur_n = got > head ? (got - head) / record : 0;
+      eof = got < need;
+      file_off += got;
+      if (got != (cur_n ? head + cur_n * record : 0))   /* a tail shorter than a record */
+        host_off = cur_base + (cur_n ? head + cur_n * record : 0);
       if (cur_n > 0) { const int rc = side(b, cur_n); if (rc) return rc; }
       T->io_ms += now_ms() - t0;
     }
@@ -159,28 +167,39 @@ int read_chunks(TextStage<Stat>& r, hipStream_t stream, int fd, const char* what
       const int64_t good = fb < (unsigned long long)prev_n ? (int64_t)fb : prev_n;
       { const int rc = deliver(prev_b, good); if (rc) return rc; }
       if (good < prev_n) {   /* not canonical from here on: the host parser's */
-        host_off = prev_base + good * record;
+        host_off = prev_base + head + good * record;
         break;
       }
       prev_n = 0;
     }
     if (cur_n > 0) {
-      C2D_TXCHK(hipMemcpyAsync(r.text_d, r.pin[b], (size_t)cur_n * record, hipMemcpyHostToDevice, stream));
+      C2D_TXCHK(hipMemcpyAsync(r.text_d, r.pin[b], (size_t)(head + cur_n * record), hipMemcpyHostToDevice, stream));
       { const int rc = enqueue(b, cur_n, k); if (rc) return rc; }
       { const int rc = r.finish(stream, b, err, errlen); if (rc) return rc; }
       prev_n = cur_n;
       prev_b = b;
-      prev_base = k * chunk_bytes;
+      prev_base = cur_base;
     }
     if (eof && prev_n == 0) break;
   }
   return host_off >= 0 ? host(host_off) : C2D_OK;
 }
 
+/* a text file: every chunk is `chunk` records with nothing before them, to the end of the file */
+template <class Stat, class Times, class Side, class Enqueue, class Deliver, class Host>
+int read_chunks(TextStage<Stat>& r, hipStream_t stream, int fd, const char* what, const char* path, int record,
+                int64_t chunk, const Stat& init, Times* T, Side&& side, Enqueue&& enqueue, Deliver&& deliver,
+                Host&& host, char* err, size_t errlen) {
+  const int64_t chunk_bytes = chunk * record;
+  return read_chunks_sized(r, stream, fd, what, path, record, 0, [&](int64_t) { return chunk_bytes; }, init, T, side,
+                           enqueue, deliver, host, err, errlen);
+}
+
 /*
  * n records of `record` bytes to the file f, `chunk` at a time: chunk k is
  * formatted and copied to pinned buffer k & 1 while chunk k - 1 goes to the
- * file.
+ * file.  `head` bytes before a chunk's records travel with them (the
+ * checkpoint's chunk head, filled on the device; 0 in the text files).
  *   produce(b, c0, m)   queues the format of records [c0, c0 + m) into the device text
  *   copy_out(b, m)      queues the copies beside the text's
  *   counts(b)           takes the route's counters of buffer b's chunk
@@ -189,9 +208,9 @@ int read_chunks(TextStage<Stat>& r, hipStream_t stream, int fd, const char* what
  * one here means the records changed under the call.
  */
 template <class Stat, class Times, class Produce, class CopyOut, class Counts, class WriteSide>
-int write_chunks(TextStage<Stat>& w, hipStream_t stream, FILE* f, const char* what, const char* path, int record,
-                 int64_t n, int64_t chunk, const Stat& init, Times* T, Produce&& produce, CopyOut&& copy_out,
-                 Counts&& counts, WriteSide&& write_side, char* err, size_t errlen) {
+int write_chunks_headed(TextStage<Stat>& w, hipStream_t stream, FILE* f, const char* what, const char* path,
+                        int record, int head, int64_t n, int64_t chunk, const Stat& init, Times* T, Produce&& produce,
+                        CopyOut&& copy_out, Counts&& counts, WriteSide&& write_side, char* err, size_t errlen) {
   const int64_t nchunks = (n + chunk - 1) / chunk;
   { const int rc = w.reset(stream, init, err, errlen); if (rc) return rc; }
   for (int64_t k = 0; k <= nchunks; k++) {
@@ -199,7 +218,7 @@ int write_chunks(TextStage<Stat>& w, hipStream_t stream, FILE* f, const char* wh
       const int b = (int)(k & 1);
       const int64_t c0 = k * chunk, m = std::min(n, c0 + chunk) - c0;
       { const int rc = produce(b, c0, m); if (rc) return rc; }
-      C2D_TXCHK(hipMemcpyAsync(w.pin[b], w.text_d, (size_t)m * record, hipMemcpyDeviceToHost, stream));
+      C2D_TXCHK(hipMemcpyAsync(w.pin[b], w.text_d, (size_t)(head + m * record), hipMemcpyDeviceToHost, stream));
       { const int rc = copy_out(b, m); if (rc) return rc; }
       { const int rc = w.finish(stream, b, err, errlen); if (rc) return rc; }
     }
@@ -217,7 +236,7 @@ int write_chunks(TextStage<Stat>& w, hipStream_t stream, FILE* f, const char* wh
       counts(b);
       if (w.stat_h[b].nonfinite)
         return efail(err, errlen, C2D_E_STATE, "%s: a non-finite value appeared while '%s' was written", what, path);
-      const size_t bytes = (size_t)m * record;
+      const size_t bytes = (size_t)(head + m * record);
       if (fwrite(w.pin[b], 1, bytes, f) != bytes)
         return efail(err, errlen, C2D_E_IO, "%s: cannot write '%s': %s", what, path, strerror(errno));
       { const int rc = write_side(b, m); if (rc) return rc; }
@@ -225,6 +244,15 @@ int write_chunks(TextStage<Stat>& w, hipStream_t stream, FILE* f, const char* wh
     }
   }
   return C2D_OK;
+}
+
+/* a text file: nothing before a chunk's records */
+template <class Stat, class Times, class Produce, class CopyOut, class Counts, class WriteSide>
+int write_chunks(TextStage<Stat>& w, hipStream_t stream, FILE* f, const char* what, const char* path, int record,
+                 int64_t n, int64_t chunk, const Stat& init, Times* T, Produce&& produce, CopyOut&& copy_out,
+                 Counts&& counts, WriteSide&& write_side, char* err, size_t errlen) {
+  return write_chunks_headed(w, stream, f, what, path, record, 0, n, chunk, init, T, produce, copy_out, counts,
+                             write_side, err, errlen);
 }
 
 }  // namespace c2d

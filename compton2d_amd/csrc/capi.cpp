@@ -25,6 +25,7 @@
 #include "reflect_host.h"
 #include "c2d_censfmt.h"
 #include "c2d_censtext.hpp"
+#include "c2d_ckpt.hpp"
 #include "c2d_evparse.hpp"
 #include "c2d_evtext.hpp"
 
@@ -208,6 +209,9 @@ struct c2d_ctx {
   c2d_cens_times cens_times = {};       /* of the last c2d_census_write* / c2d_census_read* */
   unsigned long long* cens_bad = nullptr;   /* c2d_census_read: the first record out of range */
   hipEvent_t cens_ev[2] = {nullptr, nullptr};
+  c2d_ckpt_stage* ckpt = nullptr;           /* the checkpoint calls' staging buffers (ckpt.hip) */
+  c2d_ckpt_times ckpt_times = {};           /* of the last c2d_checkpoint_write / _read */
+  bool have_kappa_prev = false;             /* a step has left its kappa table for the next (H3) */
   /* the context's own escapes binned on a second stream (c2d_obs_accumulate
    * with no events): it overlaps the next step's FP / tables / sources, and
    * the next generation-0 launch, which rewrites the event buffer, waits
@@ -587,6 +591,7 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
   c2d_evparse_free(c->evr);
   c2d_censtext_free(c->cfile);
   if (c->cens_bad) (void)hipFree(c->cens_bad);
+  c2d_ckpt_free(c->ckpt);
   for (hipEvent_t e : c->cens_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->comm) (void)ncclCommDestroy(c->comm);
@@ -1105,11 +1110,6 @@ __device__ __forceinline__ void rec_unpack(const CensusSoA& cs, int64_t d, const
   cst2(cs.ex + d, __longlong_as_double(r[4]), __longlong_as_double(r[5]));
   cst4(cs.tg + d, (uint32_t)(r[6] & 0xffffffffull), (uint32_t)(r[6] >> 32), r[7]);
 }
-/* census record i -> its slot (chunked: through the chunk list) */
-__device__ __forceinline__ int64_t cens_slot(const int32_t* clist, int64_t i) {
-  return clist ? ((int64_t)clist[i >> C2D_CCHUNK_LOG] << C2D_CCHUNK_LOG) + (i & (C2D_CCHUNK - 1)) : i;
-}
-
 /* ---- chunked census (c2d_device.hpp C2D_CCHUNK) ---- */
 /* mark the chunks of a list */
 __global__ void __launch_bounds__(256) c2d_chunk_mark(const int32_t* __restrict__ list, int64_t n,
@@ -1713,6 +1713,7 @@ static int run_step_body(c2d_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(c->kappa_prev, c->kappa_cur, sizeof(double) * c->ncell * C2D_N_VOL,
                            hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->have_kappa_prev = true;
   float ms0 = 0.f, msall = 0.f;
   if (launches > 0) {
     (void)hipEventElapsedTime(&ms0, c->ev_g0t, c->ev_g0b);
@@ -3765,5 +3766,200 @@ extern "C" int c2d_last_census_file_ms(c2d_ctx* c, double* io_ms, double* wait_m
   if (device_records) *device_records = c->cens_times.device_records;
   if (host_records) *host_records = c->cens_times.host_records;
   if (chunks) *chunks = c->cens_times.chunks;
+  return C2D_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Checkpoints (include/compton2d.h "Checkpoints"; the file in
+ * c2d_ckpt_host.h, its kernels and streaming in ckpt.hip).  Here: what the
+ * context puts into a header and demands of one, the tables' staging, and
+ * the census's store through c2d_census_append. */
+
+/* digest_sum of the grids a census record depends on */
+static uint64_t ckpt_grid_digest(const c2d_ctx* c) {
+  std::vector<uint64_t> w;
+  auto put = [&](double v) { w.push_back(c2d_bits(v)); };
+  for (int j = 1; j <= c->nz; j++) put(c->geo_h.z[j]);
+  for (int k = 1; k <= c->nr; k++) put(c->geo_h.r[k]);
+  put(c->geo_h.r[0]);
+  put(c->geo_h.z[0]);
+  for (int i = 1; i <= C2D_N_VOL; i++) put(c->geo_h.E_ph[i]);
+  for (int i = 1; i <= C2D_NPHFIELD; i++) put(c->geo_h.E_field[i]);
+  return c2d_ckpt_digest_words(w.data(), (int64_t)w.size(), 0ull).sum;
+}
+
+extern "C" int c2d_checkpoint_info(const char* path, c2d_ckpt_info* out) {
+  if (!path || !path[0] || !out) return C2D_E_ARG;
+  return c2d_ckpt_info_file(path, out, nullptr, nullptr, 0);
+}
+
+extern "C" int c2d_checkpoint_write(c2d_ctx* c, const char* path, const void* user, int64_t user_bytes,
+                                    int64_t* n_written) {
+  if (!c || !path || !path[0] || user_bytes < 0 || (user_bytes > 0 && !user)) return C2D_E_ARG;
+  if (c->census_lost) return census_lost(c, "c2d_checkpoint_write");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c2d_ckpt_header h;
+  memset(&h, 0, sizeof h);
+  h.magic = C2D_CKPT_MAGIC;
+  h.version = C2D_CKPT_VERSION;
+  h.header_bytes = C2D_CKPT_HEADER_BYTES;
+  h.nz = c->nz; h.nr = c->nr; h.nmu = c->nmu;
+  h.encoded = cens_encoded(c) ? 1 : 0;
+  h.grid_digest = ckpt_grid_digest(c);
+  h.seed = c->cfg.seed;
+  h.rank = c->cfg.rank; h.world = c->cfg.world;
+  h.ncycle = c->have_kappa_prev ? c->P.ncycle : 0;
+  h.time = c->have_kappa_prev ? c->P.time : 0.0;
+  h.dt = c->have_kappa_prev ? c->P.dt : 0.0;
+  h.sections = (c->have_kappa_prev ? C2D_CKPT_HAS_KAPPA : 0u) | (c->have_electrons ? C2D_CKPT_HAS_ELECTRONS : 0u);
+  h.n_records = c->n_census;
+  h.fp_auto_known = c->fp_auto_known ? 1 : 0;
+  h.fp_auto_exact = c->fp_auto_exact ? 1 : 0;
+  h.user_bytes = user_bytes;
+  c2d_ckpt_table tabs[3];
+  int ntabs = 0;
+  if (c->have_kappa_prev) tabs[ntabs++] = {c->kappa_prev, (int64_t)c->ncell * C2D_N_VOL};
+  if (c->have_electrons) {
+    tabs[ntabs++] = {c->f_nt, (int64_t)c->ncell * C2D_NUM_NT};
+    tabs[ntabs++] = {c->Pnt, (int64_t)c->ncell * C2D_NUM_NT};
+  }
+  char err[768] = "";
+  const int rc = c2d_ckpt_write(&c->ckpt, c->cfg.device, c->stream, c->cens[c->cur].soa(), cens_list(c), &h, tabs,
+                                ntabs, user, path, &c->ckpt_times, err, sizeof err);
+  if (!rc && n_written) *n_written = c->n_census;
+  return file_fail(c, rc, err);
+}
+
+namespace {
+struct CkptStoreDst {
+  c2d_ctx* c;
+  bool append;
+  bool storing;   /* replace: the previous census is gone */
+};
+}  // namespace
+
+static int ckpt_store_sink(void* user, const uint64_t* d_rec, int64_t n) {
+  CkptStoreDst* d = static_cast<CkptStoreDst*>(user);
+  c2d_ctx* c = d->c;
+  if (!d->append && !d->storing) {   /* the first records: the file's census replaces the context's */
+    d->storing = true;
+    c->n_census = 0;
+    if (c->chunked) c->n_clist = 0;
+    c->census_lost = false;
+  }
+  return c2d_census_append(c, d_rec, n);
+}
+
+extern "C" int c2d_checkpoint_read(c2d_ctx* c, const char* path, int64_t first, int64_t count, int32_t flags,
+                                   void* user, int64_t user_cap, int64_t* user_bytes, int64_t* n_records) {
+  if (!c || !path || !path[0] || first < 0 || count < -1 || user_cap < 0 || (user_cap > 0 && !user) ||
+      (flags & ~(C2D_CKPT_APPEND | C2D_CKPT_CENSUS_ONLY)))
+    return C2D_E_ARG;
+  if (n_records) *n_records = 0;
+  const bool append = (flags & C2D_CKPT_APPEND) != 0, census_only = (flags & C2D_CKPT_CENSUS_ONLY) != 0;
+  /* decided before anything is touched */
+  c2d_ckpt_header h;
+  c2d_ckpt_info info;
+  char err[768] = "";
+  { const int rc = c2d_ckpt_info_file(path, &info, &h, err, sizeof err); if (rc) return file_fail(c, rc, err); }
+  if (h.nz != c->nz || h.nr != c->nr || h.nmu != c->nmu)
+    return fail(c, C2D_E_ARG, "c2d_checkpoint_read: '%s' is of a %d x %d grid with %d angular bins (nz, nr, nmu), the "
+                "context of %d x %d with %d", path, h.nz, h.nr, h.nmu, c->nz, c->nr, c->nmu);
+  if (h.grid_digest != ckpt_grid_digest(c))
+    return fail(c, C2D_E_ARG, "c2d_checkpoint_read: '%s' was written on other grids (the grid digest of z, r, rmin, "
+                "zmin, E_ph, E_field differs)", path);
+  if ((h.encoded != 0) != cens_encoded(c))
+    return fail(c, C2D_E_ARG, "c2d_checkpoint_read: the azimuth encoding differs: '%s' holds %s, the context keeps %s "
+                "(comtot_mode)", path, h.encoded ? "cos(phi) and the switch bit" : "phi",
+                cens_encoded(c) ? "cos(phi) and the switch bit" : "phi");
+  if (append && c->census_lost) return census_lost(c, "c2d_checkpoint_read");
+  const int64_t lo = std::min(first, h.n_records);
+  const int64_t hi = count < 0 ? h.n_records : std::min(h.n_records, lo + std::min(count, h.n_records));
+  const int64_t n0 = append ? c->n_census : 0;
+  if (n0 + (hi - lo) > c->cfg.census_capacity)
+    return fail(c, C2D_E_CENSUS_OVERFLOW, "c2d_checkpoint_read: %lld + %lld records of '%s' > capacity %lld",
+                (long long)n0, (long long)(hi - lo), path, (long long)c->cfg.census_capacity);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  /* the tables into staging; committed when the whole call has succeeded */
+  c2d_ckpt_table tabs[3] = {};
+  int64_t words[3];
+  const int ntabs = census_only ? 0 : c2d_ckpt_tables(&h, words);
+  auto free_tabs = [&] {
+    for (c2d_ckpt_table& t : tabs)
+      if (t.d) (void)hipFree(t.d);
+  };
+  for (int i = 0; i < ntabs; i++) {
+    tabs[i].words = words[i];
+    const hipError_t e = dalloc(&tabs[i].d, (size_t)words[i]);
+    if (e != hipSuccess) {
+      free_tabs();
+      return fail(c, C2D_E_HIP, "c2d_checkpoint_read: staging a table: %s", hipGetErrorString(e));
+    }
+  }
+  CkptStoreDst d = {c, append, false};
+  int64_t got = 0;
+  int rc = c2d_ckpt_read(&c->ckpt, c->cfg.device, c->stream, path, &h, lo, hi, user, user_cap, tabs, ntabs,
+                         ckpt_store_sink, &d, &got, &c->ckpt_times, err, sizeof err);
+  if (rc) {
+    free_tabs();
+    if (err[0]) rc = fail(c, rc, "%s", err);   /* else the sink's (c2d_census_append's) message stands */
+    if (append) {   /* back to what the census held */
+      c->n_census = n0;
+      if (c->chunked) c->n_clist = (n0 + C2D_CCHUNK - 1) / C2D_CCHUNK;
+    } else if (d.storing) {   /* the previous census is gone and the file's is incomplete */
+      c->n_census = 0;
+      if (c->chunked) c->n_clist = 0;
+      c->census_lost = true;
+    }
+    return rc;
+  }
+  if (!append && !d.storing) {   /* no records: an empty census */
+    c->n_census = 0;
+    if (c->chunked) c->n_clist = 0;
+    c->census_lost = false;
+  }
+  if (!census_only) {
+    int i = 0;
+    hipError_t e = hipSuccess;
+    if (h.sections & C2D_CKPT_HAS_KAPPA) {
+      e = hipMemcpyAsync(c->kappa_prev, tabs[i++].d, sizeof(double) * c->ncell * C2D_N_VOL, hipMemcpyDeviceToDevice,
+                         c->stream);
+      c->have_kappa_prev = true;
+    }
+    if (e == hipSuccess && (h.sections & C2D_CKPT_HAS_ELECTRONS)) {
+      e = hipMemcpyAsync(c->f_nt, tabs[i++].d, sizeof(double) * c->ncell * C2D_NUM_NT, hipMemcpyDeviceToDevice,
+                         c->stream);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(c->Pnt, tabs[i++].d, sizeof(double) * c->ncell * C2D_NUM_NT, hipMemcpyDeviceToDevice,
+                           c->stream);
+      c->have_electrons = true;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    c->fp_auto_known = h.fp_auto_known != 0;
+    c->fp_auto_exact = h.fp_auto_exact != 0;
+    /* the last step's clock, so that a checkpoint of the restored context is the same file; the next
+     * c2d_set_step or c2d_set_clock sets it anew */
+    if (h.sections & C2D_CKPT_HAS_KAPPA) (void)c2d_set_clock(c, h.ncycle, h.time, h.dt);
+    if (e != hipSuccess) {
+      free_tabs();
+      return fail(c, C2D_E_HIP, "c2d_checkpoint_read: committing the tables: %s", hipGetErrorString(e));
+    }
+  }
+  free_tabs();
+  if (n_records) *n_records = got;
+  if (user_bytes) *user_bytes = h.user_bytes;
+  return C2D_OK;
+}
+
+extern "C" int c2d_last_checkpoint_ms(c2d_ctx* c, double* io_ms, double* wait_ms, double* kernel_ms, int64_t* bytes,
+                                      int32_t* chunks) {
+  if (!c) return C2D_E_ARG;
+  if (io_ms) *io_ms = c->ckpt_times.io_ms;
+  if (wait_ms) *wait_ms = c->ckpt_times.wait_ms;
+  if (kernel_ms) *kernel_ms = c->ckpt_times.kernel_ms;
+  if (bytes) *bytes = c->ckpt_times.bytes;
+  if (chunks) *chunks = c->ckpt_times.chunks;
   return C2D_OK;
 }

@@ -106,6 +106,16 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_last_census_file_ms.restype = C.c_int
     lib.c2d_last_census_file_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int64)] * 2 + [
         C.POINTER(C.c_int32)]
+    lib.c2d_checkpoint_write.restype = C.c_int
+    lib.c2d_checkpoint_write.argtypes = [vp, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    lib.c2d_checkpoint_read.restype = C.c_int
+    lib.c2d_checkpoint_read.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.c2d_checkpoint_info.restype = C.c_int
+    lib.c2d_checkpoint_info.argtypes = [C.c_char_p, C.POINTER(abi.CkptInfo)]
+    lib.c2d_last_checkpoint_ms.restype = C.c_int
+    lib.c2d_last_checkpoint_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int64),
+                                                                                C.POINTER(C.c_int32)]
     lib.c2d_census_count.restype = C.c_int
     lib.c2d_census_count.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.c2d_census_export.restype = C.c_int
@@ -226,6 +236,21 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
+
+
+def checkpoint_info(path) -> dict:
+    """The header of the checkpoint `path` (c2d_checkpoint_info): checked
+    against its digest, the file's size and the trailer; needs no GPU.
+    Raises C2DError (C2D_E_IO) for a file that fails."""
+    lib = load_library()
+    info = abi.CkptInfo()
+    rc = lib.c2d_checkpoint_info(os.fsencode(path), C.byref(info))
+    if rc != 0:
+        raise C2DError(rc, "checkpoint '%s' cannot be read or is damaged" % path)
+    d = {k: getattr(info, k) for k, _ in abi.CkptInfo._fields_ if k != "reserved"}
+    d["has_kappa"] = bool(info.sections & abi.CKPT_HAS_KAPPA)
+    d["has_electrons"] = bool(info.sections & abi.CKPT_HAS_ELECTRONS)
+    return d
 
 
 class Engine:
@@ -469,6 +494,43 @@ class Engine:
                                                      C.byref(chunks)))
         return {"io_ms": d[0].value, "wait_ms": d[1].value, "kernel_ms": d[2].value, "convert_ms": d[3].value,
                 "device_records": k[0].value, "host_records": k[1].value, "chunks": chunks.value}
+
+    # -- checkpoints: the state a step hands to the next, bit for bit -----------
+    def checkpoint_write(self, path, user: bytes = b"") -> int:
+        """Write the census (raw packed words), kappa_prev, the device
+        electron state, the FP flags and the caller's blob `user` to `path`
+        (c2d_checkpoint_write).  Returns the census records written; the
+        context is unchanged."""
+        user = bytes(user)
+        n = C.c_int64()
+        buf = C.create_string_buffer(user, len(user)) if user else None
+        self._check(self.lib.c2d_checkpoint_write(self.ctx, os.fsencode(path), buf, len(user), C.byref(n)))
+        return n.value
+
+    def checkpoint_read(self, path, first: int = 0, count: int = -1, append: bool = False,
+                        census_only: bool = False):
+        """Restore records [first, first + count) of the checkpoint's census
+        (count = -1: to the end) and, unless census_only, its tables and FP
+        flags (c2d_checkpoint_read).  append: behind the present census.
+        Returns (records stored, the user blob)."""
+        flags = (abi.CKPT_APPEND if append else 0) | (abi.CKPT_CENSUS_ONLY if census_only else 0)
+        info = abi.CkptInfo()
+        ub = 0
+        if self.lib.c2d_checkpoint_info(os.fsencode(path), C.byref(info)) == 0:
+            ub = info.user_bytes
+        buf = C.create_string_buffer(max(ub, 1))
+        n, got = C.c_int64(), C.c_int64()
+        self._check(self.lib.c2d_checkpoint_read(self.ctx, os.fsencode(path), int(first), int(count), flags, buf, ub,
+                                                 C.byref(got), C.byref(n)))
+        return n.value, buf.raw[:min(ub, got.value)]
+
+    def last_checkpoint(self) -> dict:
+        """Timings and counts of the last checkpoint call (c2d_last_checkpoint_ms)."""
+        d = [C.c_double() for _ in range(3)]
+        nb, ch = C.c_int64(), C.c_int32()
+        self._check(self.lib.c2d_last_checkpoint_ms(self.ctx, *[C.byref(v) for v in d], C.byref(nb), C.byref(ch)))
+        return {"io_ms": d[0].value, "wait_ms": d[1].value, "kernel_ms": d[2].value, "bytes": nb.value,
+                "chunks": ch.value}
 
     def last_kernel_ms(self):
         """(generation-0 kernel ms, all launches ms, launches) of the last step (HIP events)."""

@@ -559,6 +559,123 @@ int  c2d_last_census_file_ms(c2d_ctx* ctx, double* io_ms, double* wait_ms, doubl
                              double* convert_ms, int64_t* device_records, int64_t* host_records,
                              int32_t* chunks);
 
+/* Checkpoints: what one step hands to the next, as one binary file, bit for
+ * bit.  A checkpoint is taken between steps and holds the census (the raw
+ * words of c2d_census_pack, in the order of c2d_census_export: nothing is
+ * decoded, so the fast build's encoded azimuth and the bins a record carries
+ * travel as they are), the lagged kappa table of hazard H3 (kappa_prev), the
+ * device-resident electron state (f_nt, Pnt), the C2D_FP_AUTO decision
+ * carried from the last update, and an opaque blob of the caller's (its own
+ * state: step number, zone scalars).  NOT in a checkpoint: the tallies,
+ * escape events, reflection results and timers of the finished step (they
+ * are outputs; after a restore they read as on a fresh context), and the
+ * observer accumulations (c2d_obs_*, c2d_obs_set_*): they are sums, so a
+ * host reads them before it saves and adds them afterwards.
+ *
+ * The file (little-endian, every part 8-byte aligned; the same state gives
+ * the same bytes: no timestamps, no host names):
+ *
+ *   header, 128 bytes, as 16 words:
+ *      0 magic "C2DCKPT\0"           8 version u32, header bytes u32 (128)
+ *     16 nz i32, nr i32             24 nmu i32, encoded i32 (the census azimuth
+ *                                      column is cos(phi) + the C2D_CENS_ESW bit:
+ *                                      a C2D_COMTOT_TABLE context)
+ *     32 grid digest u64: digest_sum of the words z[nz] r[nr] rmin zmin
+ *        E_ph[400] E_field[400] (a record carries its cell and its E_ph /
+ *        E_field bins)
+ *     40 seed u64                   48 rank i32, world i32
+ *     56 ncycle i32, sections u32 (C2D_CKPT_HAS_*)
+ *     64 time f64                   72 dt f64    (the last step's clock, informational)
+ *     80 n_records i64              88 records per chunk i64
+ *     96 fp_auto_known i32, fp_auto_exact i32
+ *    104 user blob bytes i64       112 digest_sum of the padded blob
+ *    120 digest_sum of words 0..14
+ *   user blob, zero-padded to a multiple of 8
+ *   kappa_prev  [ncell][400] f64   (C2D_CKPT_HAS_KAPPA: once a step has run)
+ *   f_nt, Pnt   [ncell][200] f64 each (C2D_CKPT_HAS_ELECTRONS)
+ *      each table: (words i64, digest_sum, digest_xor), then the words
+ *   census: chunks of at most C2D_CKPT_CHUNK records (environment, read at
+ *      every call; default 1048576), all full but the last; each chunk:
+ *      (m i64, digest_sum, digest_xor), then m records of 8 u64
+ *   trailer, 24 bytes: magic "C2DCEND\0", n_records, t, where
+ *      t = mix(n_records + G) and per chunk t = mix(mix(t ^ sum) ^ xor)
+ *
+ * The digest (mod 2^64; G = 0x9E3779B97F4A7C15; mix is SplitMix64's
+ * finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *=
+ * 0x94D049BB133111EB; z ^= z >> 31): the record at index g of the census,
+ * words w0..w7, hashes to h = a8 with a0 = mix(g + G), a(k+1) = mix(ak ^ wk).
+ * A chunk's digest is (sum of h, xor of h) over its records, g counted from
+ * the census's first record: any order of reduction gives it, a change to
+ * one record changes the sum (mix is a bijection), and so do two records
+ * swapped (g enters).  Tables and the blob use the same rule on groups of 8
+ * words, the last zero-padded, g counted from the section's start.
+ * compton2d_amd/checkpoint.py is the same format in numpy. */
+#define C2D_CKPT_VERSION        1
+#define C2D_CKPT_HAS_KAPPA      1   /* sections */
+#define C2D_CKPT_HAS_ELECTRONS  2
+#define C2D_CKPT_APPEND         1   /* c2d_checkpoint_read flags */
+#define C2D_CKPT_CENSUS_ONLY    2
+typedef struct c2d_ckpt_info {
+  int32_t version, nz, nr, nmu;
+  int32_t encoded, rank, world, ncycle;
+  int32_t sections, fp_auto_known, fp_auto_exact, reserved;
+  uint64_t grid_digest, seed;
+  double time, dt;
+  int64_t n_records, chunk, user_bytes, file_bytes;
+} c2d_ckpt_info;
+/* Writes the context's state to `path`: to `path`.tmp, renamed at the end, so
+ * the file is flushed to the disk (fsync) before it takes the name;
+ * a failed call leaves an older checkpoint at `path` as it was (a path that
+ * exists and is not a regular file, /dev/null, is written in place).  user
+ * (user_bytes >= 0; NULL with 0) is the caller's blob.  *n_written = census
+ * records written (may be NULL).  The census is gathered through the chunk
+ * list and its digest computed in one kernel pass; chunks stream through two
+ * pinned host buffers, bounded by C2D_CKPT_CHUNK.  The context is unchanged.
+ * Before the first step the table sections are absent; an empty census is
+ * valid.  Errors: C2D_E_NONFINITE if a census record or a table holds a NaN
+ * or Inf (scanned before the file is opened); C2D_E_STATE if the census was
+ * lost by a failed in-place step; C2D_E_IO if the file cannot be written. */
+int  c2d_checkpoint_write(c2d_ctx* ctx, const char* path, const void* user, int64_t user_bytes,
+                          int64_t* n_written);
+/* Restores records [first, first + count) of the file's census (count = -1:
+ * to the end; a range is clipped to the file) and, unless
+ * C2D_CKPT_CENSUS_ONLY, kappa_prev, the electrons and the FP flags as far as
+ * the file holds them.  C2D_CKPT_APPEND adds the records behind the present
+ * census instead of replacing it.  user (user_cap bytes; may be NULL with 0)
+ * takes the first min(user_cap, *user_bytes) bytes of the blob; *user_bytes
+ * = its size; *n_records = records stored (all three are written only when
+ * the whole call has succeeded; c2d_checkpoint_info gives the blob's size
+ * beforehand).  A range that begins or ends
+ * inside a chunk reads and verifies the whole chunks that cover it.  Every
+ * record is checked on the device before it is stored (digest; cell in
+ * 1..nz x 1..nr, E_ph bin in 1..400, E_field bin in 0..400, the bin bytes,
+ * six finite doubles): nothing indexes a table with what a file says.
+ * Decided before anything is touched, the context unchanged: C2D_E_IO for a
+ * file that is missing, shorter than its header says, of another magic or
+ * version, or whose header or trailer fails; C2D_E_ARG, naming which, for
+ * another nz/nr/nmu, grid digest or azimuth encoding;
+ * C2D_E_CENSUS_OVERFLOW for more records than fit.  The tables are read and
+ * verified into staging and committed only when the whole call has
+ * succeeded.  A chunk or table whose digest or record check fails, or a
+ * trailer that disagrees, gives C2D_E_IO with the chunk and its byte offset
+ * in the message and stores nothing of that chunk; with C2D_CKPT_APPEND the
+ * census is then truncated back to what it held (the context is unchanged),
+ * else the census is lost as after a failed c2d_census_read: C2D_E_STATE
+ * until an import, read or truncate.  The file may come from either census
+ * layout and go into either. */
+int  c2d_checkpoint_read(c2d_ctx* ctx, const char* path, int64_t first, int64_t count, int32_t flags,
+                         void* user, int64_t user_cap, int64_t* user_bytes, int64_t* n_records);
+/* The header of a checkpoint, checked against its digest, the file's size and
+ * the trailer; needs no context and no GPU.  C2D_E_IO for a file that fails. */
+int  c2d_checkpoint_info(const char* path, c2d_ckpt_info* out);
+/* Diagnostics of the last c2d_checkpoint_write / _read: host milliseconds in
+ * file I/O and waiting for chunks, device milliseconds of the chunks' gather
+ * or verify kernels (the scan before a write and the tables' digests are not
+ * in it), the file bytes moved and the census chunks.  Any pointer may be
+ * NULL. */
+int  c2d_last_checkpoint_ms(c2d_ctx* ctx, double* io_ms, double* wait_ms, double* kernel_ms, int64_t* bytes,
+                            int32_t* chunks);
+
 /* Batched tridiagonal (Thomas with the reference's clipping) solve: one
  * zone per wavefront.  x is [ncell][nt] on the host. */
 int  c2d_fp_tridag(c2d_ctx* ctx, const c2d_fp_in* in, double* x);

@@ -20,6 +20,8 @@ module compton2d
   integer, parameter :: C2D_COMM_ID_BYTES = 128
   integer(c_int32_t), parameter :: C2D_COMTOT_EXACT = 0, C2D_COMTOT_TABLE = 1
   integer(c_int32_t), parameter :: C2D_TRK_SRC = 0, C2D_TRK_2012_11 = 1
+  integer(c_int32_t), parameter :: C2D_CKPT_HAS_KAPPA = 1, C2D_CKPT_HAS_ELECTRONS = 2
+  integer(c_int32_t), parameter :: C2D_CKPT_APPEND = 1, C2D_CKPT_CENSUS_ONLY = 2
   integer, parameter :: C2D_NCOUNTERS = 16, C2D_CNT_STEPS = 0, C2D_CNT_ESCAPES = 1, &
        C2D_CNT_CENSUS = 2
 
@@ -141,6 +143,16 @@ module compton2d
   ! ---- observer-frame binning (c2d_obs_*; postprocessing/pspt.c, plcm.c) ----
   integer, parameter :: C2D_OBS_SED = 0, C2D_OBS_LC = 1
   integer, parameter :: C2D_OBS_SET_MAX = 8     ! members of an observer set (c2d_obs_set_*)
+
+  ! a checkpoint's header as c2d_checkpoint_info reports it (c2d_ckpt_info)
+  type, bind(C) :: c2d_ckpt_info
+     integer(c_int32_t) :: version = 0, nz = 0, nr = 0, nmu = 0
+     integer(c_int32_t) :: encoded = 0, rank = 0, world = 0, ncycle = 0
+     integer(c_int32_t) :: sections = 0, fp_auto_known = 0, fp_auto_exact = 0, reserved = 0
+     integer(c_int64_t) :: grid_digest = 0, seed = 0      ! unsigned in C: the same 64 bits
+     real(c_double) :: time = 0.d0, dt = 0.d0
+     integer(c_int64_t) :: n_records = 0, chunk = 0, user_bytes = 0, file_bytes = 0
+  end type c2d_ckpt_info
 
   type, bind(C) :: c2d_obs_bins
      integer(c_int32_t) :: mode = 0
@@ -360,6 +372,51 @@ module compton2d
        integer(c_int64_t), intent(out) :: device_records, host_records
        integer(c_int32_t), intent(out) :: chunks
      end function c2d_last_census_file_ms
+
+     ! Binary checkpoints (include/compton2d.h "Checkpoints"): the census bit
+     ! for bit, kappa_prev, the device electrons, the FP flags and `user`
+     ! (c_loc of the host's own state, user_bytes of it).  Observer sums and
+     ! the finished step's tallies and events are NOT in a checkpoint.
+     integer(c_int) function c2d_checkpoint_write(ctx, path, user, user_bytes, n_written) &
+          bind(C, name='c2d_checkpoint_write')
+       import :: c_int, c_ptr, c_char, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       type(c_ptr), value :: user
+       integer(c_int64_t), value :: user_bytes
+       integer(c_int64_t), intent(out) :: n_written
+     end function c2d_checkpoint_write
+
+     ! records [first, first + count) (count = -1: to the end); flags:
+     ! C2D_CKPT_APPEND | C2D_CKPT_CENSUS_ONLY; user takes min(user_cap,
+     ! user_bytes) bytes of the blob
+     integer(c_int) function c2d_checkpoint_read(ctx, path, first, count, flags, user, user_cap, &
+          user_bytes, n_records) bind(C, name='c2d_checkpoint_read')
+       import :: c_int, c_ptr, c_char, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int64_t), value :: first, count
+       integer(c_int32_t), value :: flags
+       type(c_ptr), value :: user
+       integer(c_int64_t), value :: user_cap
+       integer(c_int64_t), intent(out) :: user_bytes, n_records
+     end function c2d_checkpoint_read
+
+     ! the header of a checkpoint; no context, no GPU
+     integer(c_int) function c2d_checkpoint_info(path, info) bind(C, name='c2d_checkpoint_info')
+       import :: c_int, c_char, c2d_ckpt_info
+       character(kind=c_char), intent(in) :: path(*)
+       type(c2d_ckpt_info), intent(out) :: info
+     end function c2d_checkpoint_info
+
+     integer(c_int) function c2d_last_checkpoint_ms(ctx, io_ms, wait_ms, kernel_ms, bytes, chunks) &
+          bind(C, name='c2d_last_checkpoint_ms')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: io_ms, wait_ms, kernel_ms
+       integer(c_int64_t), intent(out) :: bytes
+       integer(c_int32_t), intent(out) :: chunks
+     end function c2d_last_checkpoint_ms
 
      integer(c_int) function c2d_fp_set_config(ctx, fcfg) bind(C, name='c2d_fp_set_config')
        import :: c_int, c_ptr, c2d_fp_config
