@@ -16,20 +16,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/compton2d.h"
-#include "c2d_device.hpp"
+#include "c2d_ctx.hpp"
 #include "c2d_math.h"
 #include "c2d_rng.h"
-#include "pspt_host.h"
-#include "plcm_host.h"
 #include "reflect_host.h"
 #include "c2d_censfmt.h"
-#include "c2d_censtext.hpp"
-#include "c2d_ckpt.hpp"
-#include "c2d_evparse.hpp"
-#include "c2d_evtext.hpp"
-
-using namespace c2d;
 
 extern "C" int c2d_launch_transport_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
                                           int trk, int refl, hipStream_t s);
@@ -58,14 +49,6 @@ extern "C" int c2d_fp_fast_block(int ncell, int n_simd);
 extern "C" int c2d_fp_mom_build(const double* mcd, double* mom, hipStream_t stream);
 extern "C" int c2d_fp_waves(int ncell, int n_simd);
 extern "C" int c2d_launch_vem(const VemParams* P, int ncell, hipStream_t s);
-extern "C" int c2d_launch_obs_segs(const ObsDev* O, const double* const* ev, const int64_t* n, int nseg,
-                                   int grid, hipStream_t stream);
-extern "C" int c2d_launch_obs(const ObsDev* O, const double* ev, int64_t n, int grid,
-                              hipStream_t s);
-extern "C" int c2d_launch_obs_set(const ObsSetDev* Q, const double* const* ev, const int64_t* n, int nseg,
-                                  int grid, hipStream_t stream);
-extern "C" size_t c2d_obs_lds_bytes(int n_t, int n_mu, int n_e, int lds_rows);
-extern "C" int c2d_obs_block(void);
 extern "C" int c2d_launch_tridag(const double* a, const double* b, const double* c,
                                  const double* r, double* x, int ncell, int nt, hipStream_t s);
 
@@ -80,252 +63,7 @@ enum { CTL_WORK = 0, CTL_NCOUT = 1, CTL_POOLH = 2, CTL_N2 = 3, CTL_N3 = 4, CTL_N
 
 static_assert(CTL_NHARD < CTL_EVSH, "control words overlap the event counters");
 
-/* the packet store (c2d_device.hpp PktSoA) */
-struct DevPk {
-  double* d[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  uint32_t* jk = nullptr;
-  uint32_t* bins = nullptr;
-  uint32_t* ctr = nullptr;
-  uint32_t* sub = nullptr;
-  uint64_t* key = nullptr;
-  int64_t* hard = nullptr;    /* the scatter kernel's hard list (GenArgs.hard) */
-  int64_t cap = 0;
-  PktSoA soa() const {
-    PktSoA s;
-    s.rpre = d[0]; s.zpre = d[1]; s.wmu = d[2]; s.phi = d[3]; s.ew = d[4]; s.xnu = d[5];
-    s.dcen = d[6]; s.jk = jk; s.bins = bins; s.ctr = ctr; s.sub = sub; s.key = key;
-    return s;
-  }
-  void release() {
-    for (double*& p : d) { if (p) (void)hipFree(p); p = nullptr; }
-    if (jk) (void)hipFree(jk);
-    if (bins) (void)hipFree(bins);
-    if (ctr) (void)hipFree(ctr);
-    if (sub) (void)hipFree(sub);
-    if (key) (void)hipFree(key);
-    if (hard) (void)hipFree(hard);
-    jk = bins = ctr = sub = nullptr;
-    key = nullptr;
-    hard = nullptr;
-    cap = 0;
-  }
-};
-
-struct DevCensus {
-  c2d_d2* d[3] = {nullptr, nullptr, nullptr};   /* rz, wp, ex (CensusSoA) */
-  c2d_u4* tg = nullptr;
-  CensusSoA soa() const {
-    CensusSoA s;
-    s.rz = d[0]; s.wp = d[1]; s.ex = d[2]; s.tg = tg;
-    return s;
-  }
-};
-
 }  // namespace
-
-/* host side of one member of the observer set (c2d_obs_set_*) */
-struct ObsSetHost {
-  int kind = 0;                               /* 0 raw bins, 1 pspt deck, 2 plcm deck */
-  std::vector<double> edges;                  /* t0 t1 mu0 mu1 E0 E1 */
-  double* hist = nullptr;                     /* F, F2, count: 3 x n_t x n_mu x n_e */
-  double* red = nullptr;                      /* world_sum reduction buffer, same size (decks only) */
-  c2d_pspt_deck pspt;
-  std::vector<c2d_plcm_deck> plcm;            /* one element when kind == 2 */
-};
-
-struct c2d_ctx {
-  Geo geo_h;                  /* host copy of the grids (census import's bin lookups) */
-  c2d_config cfg;
-  int nz = 0, nr = 0, ncell = 0, nmu = 0, nslot = 0;
-  std::string err;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_g0a = nullptr, ev_g0t = nullptr, ev_g0b = nullptr, ev_end = nullptr;
-  int n_cu = 0, max_grid = 0, lds_cells = 0;
-  size_t lds_max = 64 * 1024;   /* LDS bytes a workgroup may allocate */
-  size_t lds_bytes = 0;
-  /* generation 0 as probe bundles (c2d_bundle_kernel): its LDS and grid */
-  int bundle = 1, bundle_grid = 0;
-  int src_grid = 0, sc_grid = 0;   /* CUs x resident blocks of the source / scatter kernels */
-  size_t bundle_lds = 0;
-  int evq_cap = 0;                 /* entries of a wave's escape queue in LDS (KParams.evq_cap) */
-  /* census SoA(s) of cens_phys records each.  Double-buffered:
-   * census_capacity + one append chunk per wave slot; the compaction's work
-   * lists (cscan_cap slots each).  Chunked (census_inplace, c2d_device.hpp
-   * C2D_CCHUNK): nchunks chunks, the census's chunk list (clist[ccur],
-   * n_clist chunks, all full but the last) and the next step's. */
-  int64_t cens_phys = 0;
-  uint32_t cens_chunk = 64;
-  int64_t n_ws = 0;              /* wave slots: the largest grid's waves (cstate entries) */
-  int64_t* cstate = nullptr;     /* [n_ws][2] partly filled chunk per wave slot            */
-  int chunked = 0;
-  int64_t nchunks = 0;
-  int32_t* clist[2] = {nullptr, nullptr};
-  int ccur = 0;
-  int64_t n_clist = 0;
-  bool g0_launched = false;      /* this step's generation 0 has rewritten the chunked census */
-  bool census_lost = false;      /* a failed in-place step overwrote the census (c2d_run_step) */
-  int32_t* pool = nullptr;       /* [nchunks] free chunks at the step's start */
-  int32_t* out_list = nullptr;   /* [nchunks] chunks the step took            */
-  int32_t* relist = nullptr;     /* [nchunks] chunks freed and handed on      */
-  uint8_t* cflag = nullptr;      /* [nchunks] in-use / partly-filled marks    */
-  int32_t* part_id = nullptr;    /* [n_ws] partly filled chunks ...            */
-  int64_t* part_off = nullptr;   /* [n_ws + 1] ... and their records' prefix   */
-  uint64_t* tmp_rec = nullptr;   /* packed records (moves, exports)           */
-  int64_t tmp_cap = 0;
-  int64_t last_creuse = 0, last_clost = 0;
-  int64_t* cscan = nullptr;      /* [2][cscan_cap]: dead slots below W, live slots at/above W */
-  int64_t cscan_cap = 0;
-  uint32_t* ctile_cnt = nullptr;           /* [tiles][2] holes, sources per tile       */
-  unsigned long long* ctile_off = nullptr; /* [tiles][2] + totals: exclusive prefixes  */
-  uint8_t* ctile_flag = nullptr;           /* [tiles] the tile holds a chunk tail        */
-  int64_t ctile_cap = 0;
-  int last_compact_rounds = 0;
-  int64_t last_compact_moved = 0;
-  c2d_tally_layout L;
-  /* device buffers */
-  Geo* geo = nullptr;
-  double *gnt = nullptr, *kappa_cur = nullptr, *kappa_prev = nullptr, *eps_tot = nullptr,
-         *eps_th = nullptr, *f_nt = nullptr, *Pnt = nullptr, *n_e = nullptr, *vfrac = nullptr,
-         *ewsv = nullptr, *surf_ew = nullptr, *surf_tbb = nullptr, *tbbl = nullptr;
-  int64_t *vol_prefix = nullptr, *surf_prefix = nullptr;
-  int32_t* surf_spec = nullptr;
-  SpecDev* spectra = nullptr;
-  std::vector<double*> spec_bufs;
-  int n_spectra = 0;
-  double* comtab = nullptr;
-  double* comS = nullptr;
-  DevCensus cens[2];         /* census_inplace: cens[0] only; else in / out buffers */
-  int cur = 0;               /* the buffer holding the census */
-  int64_t n_census = 0;      /* live records: cens[cur][0, n_census) */
-  double* ev = nullptr;
-  int64_t n_ev = 0;
-  int64_t ev_cnt[C2D_EV_SHARDS] = {};   /* events in each shard of the buffer (last step) */
-  bool ev_stepped = false;              /* a step has filled (or emptied) the event buffer */
-  c2d_evt_writer* evt = nullptr;        /* c2d_events_write's staging buffers (evtext.hip) */
-  c2d_evt_times evt_times = {};         /* of the last c2d_events_write* */
-  c2d_evt_reader* evr = nullptr;        /* c2d_events_read's staging buffers (evparse.hip) */
-  c2d_evr_times evr_times = {};         /* of the last c2d_events_read / c2d_obs*_accumulate_file */
-  c2d_cens_file* cfile = nullptr;       /* the census file calls' staging buffers (censtext.hip) */
-  c2d_cens_times cens_times = {};       /* of the last c2d_census_write* / c2d_census_read* */
-  unsigned long long* cens_bad = nullptr;   /* c2d_census_read: the first record out of range */
-  hipEvent_t cens_ev[2] = {nullptr, nullptr};
-  c2d_ckpt_stage* ckpt = nullptr;           /* the checkpoint calls' staging buffers (ckpt.hip) */
-  c2d_ckpt_times ckpt_times = {};           /* of the last c2d_checkpoint_write / _read */
-  bool have_kappa_prev = false;             /* a step has left its kappa table for the next (H3) */
-  /* the context's own escapes binned on a second stream (c2d_obs_accumulate
-   * with no events): it overlaps the next step's FP / tables / sources, and
-   * the next generation-0 launch, which rewrites the event buffer, waits
-   * for it (obs_settle reads its time when the host needs the result) */
-  hipStream_t obs_stream = nullptr;
-  hipEvent_t ev_obs_src = nullptr, ev_obs_a = nullptr, ev_obs_b = nullptr;
-  bool obs_inflight = false;
-  int64_t ev_cap_sh = 0;                /* per-shard capacity                             */
-  ScatRec *q2[2] = {nullptr, nullptr}, *q3[2] = {nullptr, nullptr};
-  DevPk pk;
-  double* T = nullptr;
-  double* T_own = nullptr;
-  double* nf_rep = nullptr;     /* C2D_NF_REPL x ncell x nphfield */
-  unsigned long long* ctl = nullptr;
-  int32_t* derr = nullptr;
-  KParams* dP = nullptr;
-  /* host state of the current step */
-  KParams P;
-  bool have_step = false;
-  bool have_electrons = false;  /* f_nt/Pnt hold an electron state (C2D_DEV_ELECTRONS) */
-  bool have_vem = false;        /* vem_* hold the last c2d_volume_em tables (C2D_DEV_EMISSION) */
-  int32_t* mono_flag = nullptr;
-  /* Compton reflection (cfg.cr_sent != 0): the tables on the device (cr_sent
-   * 1..3; E_ref | P_ref | W_abs in one allocation), the step's Ed_ref[nr] +
-   * three counts, and a buffer of the same size for the world sum */
-  double* refl_tab = nullptr;
-  double* refl_out = nullptr;
-  double* refl_red = nullptr;
-  bool refl_stepped = false;     /* a step has run: c2d_reflect_result has something to return */
-  /* RCCL communicator of the tally all-reduce (c2d_comm_init) */
-  ncclComm_t comm = nullptr;
-  int comm_rank = 0, comm_world = 1;
-  int64_t n_vol_global = 0, n_surf_global = 0;
-  int eps_linear = 0;
-  uint16_t* cdf_guide = nullptr;   /* [2][ncell][C2D_CDF_GUIDE + 1] (c2d_cdf_guide) */
-  bool cdf_guide_on = false;
-  std::vector<double> h_stage;
-  double last_g0_ms = 0.0, last_all_ms = 0.0;
-  float last_src_ms = 0.f;
-  unsigned long long last_prof[C2D_TR_PROF_WORDS] = {};  /* transport section counters */
-  int64_t last_g0_steps = 0;
-  double egg_min = 0.0;          /* E_field(1)^2 / E_field(2) (census n_field threshold) */
-  int64_t last_g0_paths = 0, last_all_paths = 0;   /* lane path-steps (C2D_CNT_PATHS_INT) */
-  int last_launches = 0;
-  /* Fokker-Planck */
-  bool fp_ready = false;
-  c2d_fp_config fpc;
-  double *fp_FT = nullptr, *fp_mcd = nullptr, *fp_zin = nullptr, *fp_fin = nullptr, *fp_Pin = nullptr,
-         *fp_nf = nullptr, *fp_fout = nullptr, *fp_Pout = nullptr, *fp_zout = nullptr;
-  int32_t* fp_err = nullptr;
-  unsigned long long* fp_gb_key = nullptr;   /* gamma_bar memo (fp.hip GbMemo) */
-  double* fp_gb_val = nullptr;
-  int32_t fp_mode = C2D_FP_EXACT;             /* c2d_fp_set_mode */
-  unsigned long long* fpf_gb_key = nullptr;  /* the fast kernel's own gamma_bar memo */
-  double* fpf_gb_val = nullptr;
-  FpParams* fp_dP = nullptr;                 /* FpParams in device memory (fast kernel) */
-  int32_t* fpf_zq = nullptr;                 /* fast kernel: zone queue head + order [1 + ncell] */
-  double* fpf_mom = nullptr;                 /* fast kernel: McDonald moment table              */
-  std::vector<int32_t> fpf_order;            /* zones by the last update's sub-steps, costliest first */
-  bool fpf_ordered = false;                  /* fpf_order holds a measured order */
-  /* C2D_FP_AUTO: the next update's choice, from the last update */
-  bool fp_auto_known = false, fp_auto_exact = false;
-  int32_t last_fp_mode = -1;
-  float last_fp_ms = 0.f;
-  int last_fp_waves = 0;
-  /* emission / absorption tables (c2d_volume_em) */
-  double *vem_zin = nullptr, *vem_fnt = nullptr, *vem_eph = nullptr, *vem_kap = nullptr,
-         *vem_et = nullptr, *vem_eh = nullptr, *vem_zout = nullptr;
-  float last_vem_ms = 0.f;
-  /* observer-frame binning */
-  bool obs_ready = false;
-  ObsDev obs;
-  double *obs_edges = nullptr, *obs_hist = nullptr, *obs_ev = nullptr;
-  double* pspt_red = nullptr;                 /* world_sum reduction buffer, 2 x n_t x n_e */
-  c2d_pspt_deck pspt;                         /* c2d_obs_begin_pspt's deck */
-  bool pspt_on = false;
-  int64_t obs_ev_cap = 0;
-  int obs_wg_per_cu = 1;
-  double obs_ms = 0.0;
-  /* observer set: several binnings filled in one pass (c2d_obs_set_*); its
-   * asynchronous launch shares obs_stream and the in-flight fence above */
-  ObsSetDev oset = {};
-  std::vector<ObsSetHost> oset_h;
-  double* oset_edges = nullptr;
-  bool oset_started = false;                  /* accumulated since the last clear */
-  bool obs_inflight_set = false;              /* the launch in flight is the set's */
-  int oset_wg_per_cu = 1;
-  int32_t oset_launches = 0;
-  double oset_ms = 0.0;
-};
-
-static int fail(c2d_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  return code;
-}
-
-#define HIPCHK(c, x)                                                                   \
-  do {                                                                                 \
-    hipError_t e_ = (x);                                                               \
-    if (e_ != hipSuccess)                                                              \
-      return fail((c), C2D_E_HIP, "%s:%d %s: %s", __FILE__, __LINE__, #x,              \
-                  hipGetErrorString(e_));                                              \
-  } while (0)
-
-template <class T>
-static hipError_t dalloc(T** p, size_t n) {
-  if (n == 0) n = 1;
-  return hipMalloc((void**)p, n * sizeof(T));
-}
 
 extern "C" const char* c2d_version(void) { return "compton2d_amd 0.1.0 (gfx950)"; }
 
@@ -387,10 +125,7 @@ extern "C" int c2d_init(const c2d_config* cfg, c2d_ctx** out) {
 
   HIPCHK(c, hipSetDevice(cfg->device));
   HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(c, hipStreamCreateWithFlags(&c->obs_stream, hipStreamNonBlocking));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_obs_src, hipEventDisableTiming));
-  HIPCHK(c, hipEventCreate(&c->ev_obs_a));
-  HIPCHK(c, hipEventCreate(&c->ev_obs_b));
+  { const int rc = obs_init(c); if (rc) return rc; }
   HIPCHK(c, hipEventCreate(&c->ev_g0a));
   HIPCHK(c, hipEventCreate(&c->ev_g0b));
   HIPCHK(c, hipEventCreate(&c->ev_g0t));
@@ -585,7 +320,7 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->obs_stream) (void)hipStreamSynchronize(c->obs_stream);   /* it reads the event buffer */
+  obs_release(c);
   if (c->mono_flag) (void)hipFree(c->mono_flag);
   c2d_evtext_free(c->evt);
   c2d_evparse_free(c->evr);
@@ -612,13 +347,7 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
   void* rptrs[] = {c->refl_tab, c->refl_out, c->refl_red};
   for (void* p : rptrs)
     if (p) (void)hipFree(p);
-  void* optrs[] = {c->obs_edges, c->obs_hist, c->obs_ev, c->pspt_red, c->cdf_guide, c->oset_edges};
-  for (void* p : optrs)
-    if (p) (void)hipFree(p);
-  for (ObsSetHost& m : c->oset_h) {
-    if (m.hist) (void)hipFree(m.hist);
-    if (m.red) (void)hipFree(m.red);
-  }
+  if (c->cdf_guide) (void)hipFree(c->cdf_guide);
   void* vptrs[] = {c->vem_zin, c->vem_fnt, c->vem_eph, c->vem_kap, c->vem_et, c->vem_eh, c->vem_zout};
   for (void* q : vptrs)
     if (q) (void)hipFree(q);
@@ -632,11 +361,6 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
   if (c->ev_g0b) (void)hipEventDestroy(c->ev_g0b);
   if (c->ev_g0t) (void)hipEventDestroy(c->ev_g0t);
   if (c->ev_end) (void)hipEventDestroy(c->ev_end);
-  if (c->obs_stream) (void)hipStreamSynchronize(c->obs_stream);
-  if (c->ev_obs_src) (void)hipEventDestroy(c->ev_obs_src);
-  if (c->ev_obs_a) (void)hipEventDestroy(c->ev_obs_a);
-  if (c->ev_obs_b) (void)hipEventDestroy(c->ev_obs_b);
-  if (c->obs_stream) (void)hipStreamDestroy(c->obs_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1558,9 +1282,9 @@ static int run_step_body(c2d_ctx* c) {
   unsigned long long nq[CTL_CNT + C2D_CNT_PATHS_INT + 1 - CTL_N2];
   /* ---- generation 0: census + sampled sources ---- */
   {
-    /* the last step's events may still be binned on obs_stream: they are
+    /* the last step's events may still be binned on the observer's stream: they are
      * rewritten from here on (the tables, FP and budgets ran beside it) */
-    if (c->obs_inflight) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_obs_b, 0));
+    { const int rc = obs_fence(c, c->stream); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(c->ev_g0a, c->stream));
     if (n_src > 0) {
       int rc = launch_src(c->dP, aux_grid(n_src, c->src_grid), c->stream);
@@ -2762,559 +2486,6 @@ extern "C" int c2d_last_vem_ms(c2d_ctx* c, double* ms) {
 }
 
 /* ------------------------------------------------------------------ */
-/* observer-frame binning (postprocessing/pspt.c, plcm.c)               */
-/* ------------------------------------------------------------------ */
-static int obs_settle(c2d_ctx* c);
-
-extern "C" int c2d_obs_begin(c2d_ctx* c, const c2d_obs_bins* b) {
-  if (!c || !b) return C2D_E_ARG;
-  if ((b->mode != C2D_OBS_SED && b->mode != C2D_OBS_LC) || b->n_t < 1 || b->n_t > C2D_OBS_MAX_T ||
-      b->n_mu < 1 || b->n_mu > C2D_OBS_MAX_MU || b->n_e < 1 || b->n_e > C2D_OBS_MAX_E ||
-      !b->t0 || !b->t1 || !b->mu0 || !b->mu1 || !b->E0 || !b->E1 || !(b->gam_bulk >= 1.0))
-    return fail(c, C2D_E_ARG, "c2d_obs_begin: bad binning");
-  if (b->mode == C2D_OBS_SED && b->n_mu != 1)
-    return fail(c, C2D_E_ARG, "c2d_obs_begin: the SED mode has one angular window");
-  /* a new binning ends any pspt deck: c2d_obs_begin_pspt sets it again */
-  c->pspt_on = false;
-  c->obs_ready = false;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }   /* the histogram is about to go */
-  if (c->obs_edges) (void)hipFree(c->obs_edges);
-  if (c->obs_hist) (void)hipFree(c->obs_hist);
-  c->obs_edges = c->obs_hist = nullptr;
-  const int ne = 2 * (b->n_t + b->n_mu + b->n_e);
-  std::vector<double> h;
-  h.reserve(ne);
-  h.insert(h.end(), b->t0, b->t0 + b->n_t);
-  h.insert(h.end(), b->t1, b->t1 + b->n_t);
-  h.insert(h.end(), b->mu0, b->mu0 + b->n_mu);
-  h.insert(h.end(), b->mu1, b->mu1 + b->n_mu);
-  h.insert(h.end(), b->E0, b->E0 + b->n_e);
-  h.insert(h.end(), b->E1, b->E1 + b->n_e);
-  HIPCHK(c, dalloc(&c->obs_edges, (size_t)ne));
-  HIPCHK(c, hipMemcpy(c->obs_edges, h.data(), ne * sizeof(double), hipMemcpyHostToDevice));
-  const size_t nh = (size_t)b->n_t * b->n_mu * b->n_e;
-  HIPCHK(c, dalloc(&c->obs_hist, 3 * nh));
-  HIPCHK(c, hipMemset(c->obs_hist, 0, 3 * nh * sizeof(double)));
-  ObsDev& O = c->obs;
-  O.gam_bulk = b->gam_bulk; O.rmax = b->rmax; O.t_offset = b->t_offset;
-  O.mode = b->mode; O.n_t = b->n_t; O.n_mu = b->n_mu; O.n_e = b->n_e;
-  O.t0 = c->obs_edges; O.t1 = O.t0 + b->n_t; O.mu0 = O.t1 + b->n_t; O.mu1 = O.mu0 + b->n_mu;
-  O.E0 = O.mu1 + b->n_mu; O.E1 = O.E0 + b->n_e;
-  O.F = c->obs_hist; O.F2 = O.F + nh; O.cnt = O.F2 + nh;
-  /* privatise in LDS when the three histograms fit next to the edges */
-  /* privatise as many leading time rows in LDS as fit (all of them for the
-   * usual SED); later rows go to wave-aggregated global atomics */
-  {
-    const size_t edges = c2d_obs_lds_bytes(b->n_t, b->n_mu, b->n_e, 0);
-    const size_t row = c2d_obs_lds_bytes(0, b->n_mu, b->n_e, 1) - c2d_obs_lds_bytes(0, b->n_mu, b->n_e, 0);
-    /* 1 KiB for the kernel's static segment table (observe.hip ObsSegs) */
-    const size_t avail = c->lds_max > edges + 1024 ? c->lds_max - edges - 1024 : 0;
-    O.lds_rows = (int)std::min<size_t>((size_t)b->n_t, avail / row);
-    const size_t bytes = c2d_obs_lds_bytes(b->n_t, b->n_mu, b->n_e, O.lds_rows);
-    /* workgroups per CU that fit the CU's 160 KiB of LDS, at most 4 */
-    c->obs_wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / (bytes + 1024)));
-  }
-  auto sorted = [](const double* lo, const double* hi, int n) {
-    for (int i = 1; i < n; i++)
-      if (!(lo[i] >= lo[i - 1]) || !(hi[i] >= hi[i - 1])) return 0;
-    return 1;
-  };
-  O.sorted_t = sorted(b->t0, b->t1, b->n_t);
-  O.sorted_mu = sorted(b->mu0, b->mu1, b->n_mu);
-  O.sorted_e = sorted(b->E0, b->E1, b->n_e);
-  c->obs_ms = 0.0;
-  c->obs_ready = true;
-  return C2D_OK;
-}
-
-/* Wait for an asynchronous binning of the context's own events (obs_stream)
- * and add its kernel time. */
-static int obs_settle(c2d_ctx* c) {
-  if (!c->obs_inflight) return C2D_OK;
-  c->obs_inflight = false;
-  HIPCHK(c, hipEventSynchronize(c->ev_obs_b));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev_obs_a, c->ev_obs_b);
-  if (c->obs_inflight_set) c->oset_ms += ms; else c->obs_ms += ms;
-  c->obs_inflight_set = false;
-  return C2D_OK;
-}
-
-/* Bin `nseg` event segments (device pointer, count) back to back on the
- * context's stream; one event pair and one synchronisation around them all. */
-static int obs_launch_segments(c2d_ctx* c, const double* const* ev, const int64_t* m, int nseg) {
-  int64_t tot = 0;
-  for (int s = 0; s < nseg; s++) tot += m[s];
-  if (tot == 0) return C2D_OK;
-  /* enough blocks to fill the chip, each privatising its own histogram */
-  const int64_t bs = c2d_obs_block();
-  HIPCHK(c, hipEventRecord(c->ev_g0a, c->stream));
-  {   /* every segment in one launch */
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * c->obs_wg_per_cu, (tot + bs - 1) / bs));
-    int rc = c2d_launch_obs_segs(&c->obs, ev, m, nseg, grid, c->stream);
-    if (rc) return fail(c, C2D_E_HIP, "obs launch: %s", hipGetErrorString((hipError_t)rc));
-  }
-  HIPCHK(c, hipEventRecord(c->ev_g0b, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev_g0a, c->ev_g0b);
-  c->obs_ms += ms;
-  return C2D_OK;
-}
-
-static int obs_launch(c2d_ctx* c, const double* ev, int64_t m) {
-  return obs_launch_segments(c, &ev, &m, 1);
-}
-
-extern "C" int c2d_obs_accumulate(c2d_ctx* c, const double* events, int64_t n) {
-  if (!c) return C2D_E_ARG;
-  if (!c->obs_ready) return fail(c, C2D_E_STATE, "c2d_obs_begin must precede c2d_obs_accumulate");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  if (!events) {
-    const double* seg[C2D_EV_SHARDS];
-    int64_t cnt[C2D_EV_SHARDS];
-    int64_t tot = 0;
-    for (int sh = 0; sh < C2D_EV_SHARDS; sh++) {
-      seg[sh] = c->ev + (size_t)sh * c->ev_cap_sh * C2D_EVENT_WORDS;
-      cnt[sh] = c->ev_cnt[sh];
-      tot += cnt[sh];
-    }
-    const char* e = getenv("C2D_OBS_ASYNC");
-    if ((e && e[0] == '0') || tot == 0) return obs_launch_segments(c, seg, cnt, C2D_EV_SHARDS);
-    /* on obs_stream, after the step that wrote the events; the next
-     * generation-0 launch waits for it (run_step_body) */
-    HIPCHK(c, hipEventRecord(c->ev_obs_src, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->obs_stream, c->ev_obs_src, 0));
-    const int64_t bs = c2d_obs_block();
-    HIPCHK(c, hipEventRecord(c->ev_obs_a, c->obs_stream));
-    /* one launch per shard: between the short launches the FP update's
-     * workgroups (69 KB of LDS each) find room beside them (binning all
-     * shards in one launch beside the FP slowed it 1.26 -> 2.3-2.8 ms,
-     * at one or two workgroups per CU) */
-    for (int s = 0; s < C2D_EV_SHARDS; s++) {
-      if (cnt[s] == 0) continue;
-      const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * c->obs_wg_per_cu, (cnt[s] + bs - 1) / bs));
-      int rc = c2d_launch_obs(&c->obs, seg[s], cnt[s], grid, c->obs_stream);
-      if (rc) return fail(c, C2D_E_HIP, "obs launch: %s", hipGetErrorString((hipError_t)rc));
-    }
-    HIPCHK(c, hipEventRecord(c->ev_obs_b, c->obs_stream));
-    c->obs_inflight = true;
-    return C2D_OK;
-  }
-  if (n < 0) return C2D_E_ARG;
-  if (n > c->obs_ev_cap) {
-    if (c->obs_ev) (void)hipFree(c->obs_ev);
-    c->obs_ev = nullptr;
-    HIPCHK(c, dalloc(&c->obs_ev, (size_t)n * C2D_EVENT_WORDS));
-    c->obs_ev_cap = n;
-  }
-  if (n) HIPCHK(c, hipMemcpy(c->obs_ev, events, (size_t)n * C2D_EVENT_WORDS * sizeof(double),
-                             hipMemcpyHostToDevice));
-  return obs_launch(c, c->obs_ev, n);
-}
-
-extern "C" int c2d_obs_accumulate_device(c2d_ctx* c, const double* d_events, int64_t n) {
-  if (!c || !d_events || n < 0) return C2D_E_ARG;
-  if (!c->obs_ready) return fail(c, C2D_E_STATE, "c2d_obs_begin must precede c2d_obs_accumulate_device");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  return obs_launch(c, d_events, n);
-}
-
-extern "C" int c2d_obs_result(c2d_ctx* c, double* F, double* F2, double* count, double* kernel_ms) {
-  if (!c) return C2D_E_ARG;
-  if (!c->obs_ready) return fail(c, C2D_E_STATE, "c2d_obs_begin must precede c2d_obs_result");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  const size_t nh = (size_t)c->obs.n_t * c->obs.n_mu * c->obs.n_e;
-  if (F) HIPCHK(c, hipMemcpy(F, c->obs.F, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (F2) HIPCHK(c, hipMemcpy(F2, c->obs.F2, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (count) HIPCHK(c, hipMemcpy(count, c->obs.cnt, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (kernel_ms) *kernel_ms = c->obs_ms;
-  return C2D_OK;
-}
-
-/* pspt's dialogue -> the SED binning (postprocessing/pspt.c:105-205) */
-extern "C" int c2d_obs_begin_pspt(c2d_ctx* c, const char* deck) {
-  if (!c) return C2D_E_ARG;
-  c2d_pspt_deck d;
-  if (c2d_pspt_parse(deck ? deck : "", &d))
-    return fail(c, C2D_E_ARG, "c2d_obs_begin_pspt: the deck's grid has no bins or more than %d energy channels",
-                C2D_PSPT_CHMAX);
-  c2d_obs_bins b;
-  b.mode = C2D_OBS_SED; b.gam_bulk = d.gam_bulk; b.rmax = d.rmax; b.t_offset = 0.0;
-  b.n_t = d.n_t; b.t0 = d.t0; b.t1 = d.t1;
-  b.n_mu = 1; b.mu0 = &d.mu0; b.mu1 = &d.mu1;
-  b.n_e = d.n_e; b.E0 = d.E0; b.E1 = d.E1;
-  const int rc = c2d_obs_begin(c, &b);
-  if (rc != C2D_OK) return rc;
-  /* the world_sum reduction buffer lives as long as the deck, so a rank can
-   * no longer fail an allocation and skip the collective the others enter */
-  if (c->pspt_red) (void)hipFree(c->pspt_red);
-  c->pspt_red = nullptr;
-  HIPCHK(c, dalloc(&c->pspt_red, 2 * (size_t)d.n_t * d.n_e));
-  c->pspt = d;
-  c->pspt_on = true;
-  return C2D_OK;
-}
-
-/* pspt's output file from the histogram so far (postprocessing/pspt.c:323-353);
- * world_sum: summed over the context's communicator first (every rank calls,
- * rank 0 writes) */
-extern "C" int c2d_obs_write_pspt(c2d_ctx* c, const char* path, int32_t factor, int32_t world_sum) {
-  if (!c) return C2D_E_ARG;
-  if (!c->pspt_on || !c->obs_ready) return fail(c, C2D_E_STATE, "c2d_obs_write_pspt: c2d_obs_begin_pspt first");
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  if (c->obs.mode != C2D_OBS_SED || c->obs.n_mu != 1 || c->obs.n_t != c->pspt.n_t || c->obs.n_e != c->pspt.n_e ||
-      !c->pspt_red)
-    return fail(c, C2D_E_STATE, "c2d_obs_write_pspt: the binning is not the pspt deck's");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const size_t nh = (size_t)c->obs.n_t * c->obs.n_mu * c->obs.n_e;
-  std::vector<double> F(nh), cnt(nh);
-  if (world_sum) {
-    if (!c->comm) return fail(c, C2D_E_STATE, "c2d_obs_write_pspt: world_sum needs c2d_comm_init");
-    double* w = c->pspt_red;
-    HIPCHK(c, hipMemcpyAsync(w, c->obs.F, nh * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + nh, c->obs.cnt, nh * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    const ncclResult_t r = ncclAllReduce(w, w, 2 * nh, ncclDouble, ncclSum, c->comm, c->stream);
-    if (r != ncclSuccess) return fail(c, C2D_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
-    HIPCHK(c, hipMemcpyAsync(F.data(), w, nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cnt.data(), w + nh, nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->comm_rank != 0) return C2D_OK;
-  } else {
-    const int rc = c2d_obs_result(c, F.data(), nullptr, cnt.data(), nullptr);
-    if (rc != C2D_OK) return rc;
-  }
-  const char* out = (path && path[0]) ? path : c->pspt.outfile;
-  if (c2d_pspt_write(out, &c->pspt, F.data(), cnt.data(), factor))
-    return fail(c, C2D_E_IO, "c2d_obs_write_pspt: cannot write '%s'", out);
-  return C2D_OK;
-}
-
-/* ------------------------------------------------------------------ */
-/* observer sets: several SEDs and light curves in one pass            */
-/* ------------------------------------------------------------------ */
-/* The LDS plan of a set: the edges of every member, then
- * privatised leading time rows.  What the edges leave of the workgroup's
- * OBS_SET_LDS is shared out equally among the members, each taking whole
- * rows of its share (at most its n_t); what that leaves over is handed out
- * in registration order.  -1 when the edges alone do not fit. */
-static int obs_set_plan(ObsSetDev& Q, int* wg_per_cu) {
-  const int64_t budget = (OBS_SET_LDS - OBS_SET_LDS_STATIC) / (int64_t)sizeof(double);
-  int64_t ne = 0;
-  for (int j = 0; j < Q.n; j++) {
-    Q.m[j].edge_off = (int32_t)ne;
-    ne += 2 * ((int64_t)Q.m[j].n_t + Q.m[j].n_mu + Q.m[j].n_e);
-    if (ne > budget) return -1;
-  }
-  int64_t left = budget - ne;
-  const int64_t share = Q.n ? left / Q.n : 0;
-  for (int j = 0; j < Q.n; j++) {
-    const int64_t row = 3 * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
-    Q.m[j].lds_rows = (int32_t)std::min<int64_t>(Q.m[j].n_t, share / row);
-    left -= Q.m[j].lds_rows * row;
-  }
-  int64_t nh = 0;
-  for (int j = 0; j < Q.n; j++) {
-    const int64_t row = 3 * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
-    const int64_t more = std::min<int64_t>(Q.m[j].n_t - Q.m[j].lds_rows, left / row);
-    Q.m[j].lds_rows += (int32_t)more;
-    left -= more * row;
-    Q.m[j].hist_off = (int32_t)(ne + nh);
-    nh += Q.m[j].lds_rows * row;
-  }
-  Q.n_edges = (int32_t)ne;
-  Q.n_hist = (int32_t)nh;
-  /* workgroups per CU that fit the CU's 160 KiB of LDS, at most 4 */
-  const size_t bytes = (size_t)(ne + nh) * sizeof(double) + OBS_SET_LDS_STATIC;
-  *wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / bytes));
-  return 0;
-}
-
-static void obs_set_free(c2d_ctx* c) {
-  for (ObsSetHost& m : c->oset_h) {
-    if (m.hist) (void)hipFree(m.hist);
-    if (m.red) (void)hipFree(m.red);
-  }
-  c->oset_h.clear();
-  if (c->oset_edges) (void)hipFree(c->oset_edges);
-  c->oset_edges = nullptr;
-  c->oset = ObsSetDev{};
-  c->oset_started = false;
-  c->oset_launches = 0;
-  c->oset_ms = 0.0;
-}
-
-extern "C" int c2d_obs_set_clear(c2d_ctx* c) {
-  if (!c) return C2D_E_ARG;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }   /* the histograms are about to go */
-  obs_set_free(c);
-  return C2D_OK;
-}
-
-/* add a member: `h` carries its kind and deck; the edges come from `b` */
-static int obs_set_add_member(c2d_ctx* c, const c2d_obs_bins* b, ObsSetHost&& h, int32_t* id, const char* who) {
-  if ((b->mode != C2D_OBS_SED && b->mode != C2D_OBS_LC) || b->n_t < 1 || b->n_t > C2D_OBS_MAX_T ||
-      b->n_mu < 1 || b->n_mu > C2D_OBS_MAX_MU || b->n_e < 1 || b->n_e > C2D_OBS_MAX_E ||
-      !b->t0 || !b->t1 || !b->mu0 || !b->mu1 || !b->E0 || !b->E1 || !(b->gam_bulk >= 1.0))
-    return fail(c, C2D_E_ARG, "%s: bad binning", who);
-  if (b->mode == C2D_OBS_SED && b->n_mu != 1)
-    return fail(c, C2D_E_ARG, "%s: the SED mode has one angular window", who);
-  if (c->oset_started)
-    return fail(c, C2D_E_STATE, "%s: the set has accumulated events; c2d_obs_set_clear first", who);
-  if (c->oset.n >= C2D_OBS_SET_MAX)
-    return fail(c, C2D_E_ARG, "%s: a set holds at most %d members", who, C2D_OBS_SET_MAX);
-  ObsSetDev Q = c->oset;
-  ObsSetMember& M = Q.m[Q.n++];
-  M = ObsSetMember{};
-  M.gam_bulk = b->gam_bulk; M.rmax = b->rmax; M.t_offset = b->t_offset;
-  M.mode = b->mode; M.n_t = b->n_t; M.n_mu = b->n_mu; M.n_e = b->n_e;
-  auto sorted = [](const double* lo, const double* hi, int n) {
-    for (int i = 1; i < n; i++)
-      if (!(lo[i] >= lo[i - 1]) || !(hi[i] >= hi[i - 1])) return 0;
-    return 1;
-  };
-  M.sorted_t = sorted(b->t0, b->t1, b->n_t);
-  M.sorted_mu = sorted(b->mu0, b->mu1, b->n_mu);
-  M.sorted_e = sorted(b->E0, b->E1, b->n_e);
-  int wg = 1;
-  if (obs_set_plan(Q, &wg))
-    return fail(c, C2D_E_ARG, "%s: the set's bin edges (%lld B with this member) exceed the workgroup's %d B of LDS",
-                who, (long long)(sizeof(double) * (2 * ((int64_t)b->n_t + b->n_mu + b->n_e) + c->oset.n_edges)),
-                OBS_SET_LDS - OBS_SET_LDS_STATIC);
-  h.edges.clear();
-  h.edges.insert(h.edges.end(), b->t0, b->t0 + b->n_t);
-  h.edges.insert(h.edges.end(), b->t1, b->t1 + b->n_t);
-  h.edges.insert(h.edges.end(), b->mu0, b->mu0 + b->n_mu);
-  h.edges.insert(h.edges.end(), b->mu1, b->mu1 + b->n_mu);
-  h.edges.insert(h.edges.end(), b->E0, b->E0 + b->n_e);
-  h.edges.insert(h.edges.end(), b->E1, b->E1 + b->n_e);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  /* every member's edges in one device array, in the LDS order of the plan */
-  std::vector<double> all;
-  all.reserve((size_t)Q.n_edges);
-  for (const ObsSetHost& m : c->oset_h) all.insert(all.end(), m.edges.begin(), m.edges.end());
-  all.insert(all.end(), h.edges.begin(), h.edges.end());
-  const size_t nh = (size_t)b->n_t * b->n_mu * b->n_e;
-  double *d_edges = nullptr, *d_hist = nullptr, *d_red = nullptr;
-  hipError_t e = dalloc(&d_edges, all.size());
-  if (e == hipSuccess) e = dalloc(&d_hist, 3 * nh);
-  /* the world_sum reduction buffer lives as long as the member (as pspt_red) */
-  if (e == hipSuccess && h.kind) e = dalloc(&d_red, 3 * nh);
-  if (e == hipSuccess) e = hipMemcpy(d_edges, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_hist, 0, 3 * nh * sizeof(double));
-  if (e != hipSuccess) {
-    if (d_edges) (void)hipFree(d_edges);
-    if (d_hist) (void)hipFree(d_hist);
-    if (d_red) (void)hipFree(d_red);
-    return fail(c, C2D_E_HIP, "%s: %s", who, hipGetErrorString(e));
-  }
-  if (c->oset_edges) (void)hipFree(c->oset_edges);
-  c->oset_edges = d_edges;
-  M.F = d_hist; M.F2 = M.F + nh; M.cnt = M.F2 + nh;
-  Q.edges = d_edges;
-  h.hist = d_hist;
-  h.red = d_red;
-  if (id) *id = Q.n - 1;
-  c->oset = Q;
-  c->oset_wg_per_cu = wg;
-  c->oset_h.push_back(std::move(h));
-  return C2D_OK;
-}
-
-extern "C" int c2d_obs_set_add(c2d_ctx* c, const c2d_obs_bins* b, int32_t* id) {
-  if (!c || !b) return C2D_E_ARG;
-  return obs_set_add_member(c, b, ObsSetHost{}, id, "c2d_obs_set_add");
-}
-
-extern "C" int c2d_obs_set_add_pspt(c2d_ctx* c, const char* deck, int32_t* id) {
-  if (!c) return C2D_E_ARG;
-  ObsSetHost h;
-  h.kind = 1;
-  c2d_pspt_deck& d = h.pspt;
-  if (c2d_pspt_parse(deck ? deck : "", &d))
-    return fail(c, C2D_E_ARG, "c2d_obs_set_add_pspt: the deck's grid has no bins or more than %d energy channels",
-                C2D_PSPT_CHMAX);
-  c2d_obs_bins b;
-  b.mode = C2D_OBS_SED; b.gam_bulk = d.gam_bulk; b.rmax = d.rmax; b.t_offset = 0.0;
-  b.n_t = d.n_t; b.t0 = d.t0; b.t1 = d.t1;
-  b.n_mu = 1; b.mu0 = &d.mu0; b.mu1 = &d.mu1;
-  b.n_e = d.n_e; b.E0 = d.E0; b.E1 = d.E1;
-  return obs_set_add_member(c, &b, std::move(h), id, "c2d_obs_set_add_pspt");
-}
-
-extern "C" int c2d_obs_set_add_plcm(c2d_ctx* c, const char* deck, int32_t* id) {
-  if (!c) return C2D_E_ARG;
-  ObsSetHost h;
-  h.kind = 2;
-  h.plcm.resize(1);
-  c2d_plcm_deck& d = h.plcm[0];
-  if (c2d_plcm_parse(deck ? deck : "", &d))
-    return fail(c, C2D_E_ARG, "c2d_obs_set_add_plcm: the deck has no angular bin, an empty region or more than %d "
-                "energy channels", C2D_PLCM_CHMAX);
-  c2d_obs_bins b;
-  b.mode = C2D_OBS_LC; b.gam_bulk = d.gam_bulk; b.rmax = d.rmax; b.t_offset = d.t_offset;
-  b.n_t = d.n_t; b.t0 = d.t0; b.t1 = d.t1;
-  b.n_mu = d.n_mu; b.mu0 = d.mu0; b.mu1 = d.mu1;
-  b.n_e = d.n_e; b.E0 = d.E0; b.E1 = d.E1;
-  return obs_set_add_member(c, &b, std::move(h), id, "c2d_obs_set_add_plcm");
-}
-
-static int obs_set_grid(const c2d_ctx* c, int64_t tot) {
-  const int64_t bs = c2d_obs_block();
-  return (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * c->oset_wg_per_cu, (tot + bs - 1) / bs));
-}
-
-/* one launch over the segments on the context's stream, waited for */
-static int obs_set_launch_sync(c2d_ctx* c, const double* const* ev, const int64_t* m, int nseg) {
-  int64_t tot = 0;
-  for (int s = 0; s < nseg; s++) tot += m[s];
-  if (tot == 0) return C2D_OK;
-  HIPCHK(c, hipEventRecord(c->ev_g0a, c->stream));
-  const int rc = c2d_launch_obs_set(&c->oset, ev, m, nseg, obs_set_grid(c, tot), c->stream);
-  if (rc) return fail(c, C2D_E_HIP, "obs set launch: %s", hipGetErrorString((hipError_t)rc));
-  HIPCHK(c, hipEventRecord(c->ev_g0b, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev_g0a, c->ev_g0b);
-  c->oset_ms += ms;
-  c->oset_launches++;
-  return C2D_OK;
-}
-
-extern "C" int c2d_obs_set_accumulate(c2d_ctx* c, const double* events, int64_t n) {
-  if (!c) return C2D_E_ARG;
-  if (c->oset.n < 1) return fail(c, C2D_E_STATE, "c2d_obs_set_accumulate: the set is empty");
-  if (events && n < 0) return C2D_E_ARG;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  c->oset_started = true;
-  if (!events) {
-    const double* seg[C2D_EV_SHARDS];
-    int64_t cnt[C2D_EV_SHARDS];
-    int64_t tot = 0;
-    for (int sh = 0; sh < C2D_EV_SHARDS; sh++) {
-      seg[sh] = c->ev + (size_t)sh * c->ev_cap_sh * C2D_EVENT_WORDS;
-      cnt[sh] = c->ev_cnt[sh];
-      tot += cnt[sh];
-    }
-    const char* e = getenv("C2D_OBS_ASYNC");
-    if ((e && e[0] == '0') || tot == 0) return obs_set_launch_sync(c, seg, cnt, C2D_EV_SHARDS);
-    /* on obs_stream, after the step that wrote the events; the next
-     * generation-0 launch waits for ev_obs_b (run_step_body).  One launch
-     * over all shards: a set workgroup stages up to 63 KiB of edges and
-     * rows, which one launch per shard would repeat 32 times */
-    HIPCHK(c, hipEventRecord(c->ev_obs_src, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->obs_stream, c->ev_obs_src, 0));
-    HIPCHK(c, hipEventRecord(c->ev_obs_a, c->obs_stream));
-    const int rc = c2d_launch_obs_set(&c->oset, seg, cnt, C2D_EV_SHARDS, obs_set_grid(c, tot), c->obs_stream);
-    if (rc) return fail(c, C2D_E_HIP, "obs set launch: %s", hipGetErrorString((hipError_t)rc));
-    HIPCHK(c, hipEventRecord(c->ev_obs_b, c->obs_stream));
-    c->obs_inflight = true;
-    c->obs_inflight_set = true;
-    c->oset_launches++;
-    return C2D_OK;
-  }
-  if (n > c->obs_ev_cap) {
-    if (c->obs_ev) (void)hipFree(c->obs_ev);
-    c->obs_ev = nullptr;
-    c->obs_ev_cap = 0;
-    HIPCHK(c, dalloc(&c->obs_ev, (size_t)n * C2D_EVENT_WORDS));
-    c->obs_ev_cap = n;
-  }
-  if (n) HIPCHK(c, hipMemcpy(c->obs_ev, events, (size_t)n * C2D_EVENT_WORDS * sizeof(double),
-                             hipMemcpyHostToDevice));
-  const double* ev = c->obs_ev;
-  return obs_set_launch_sync(c, &ev, &n, 1);
-}
-
-extern "C" int c2d_obs_set_accumulate_device(c2d_ctx* c, const double* d_events, int64_t n) {
-  if (!c || !d_events || n < 0) return C2D_E_ARG;
-  if (c->oset.n < 1) return fail(c, C2D_E_STATE, "c2d_obs_set_accumulate_device: the set is empty");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  c->oset_started = true;
-  return obs_set_launch_sync(c, &d_events, &n, 1);
-}
-
-extern "C" int c2d_obs_set_shape(c2d_ctx* c, int32_t id, int32_t* n_t, int32_t* n_mu, int32_t* n_e,
-                                 int32_t* lds_rows) {
-  if (!c) return C2D_E_ARG;
-  if (id < 0 || id >= c->oset.n) return fail(c, C2D_E_ARG, "c2d_obs_set_shape: no member %d", (int)id);
-  const ObsSetMember& M = c->oset.m[id];
-  if (n_t) *n_t = M.n_t;
-  if (n_mu) *n_mu = M.n_mu;
-  if (n_e) *n_e = M.n_e;
-  if (lds_rows) *lds_rows = M.lds_rows;
-  return C2D_OK;
-}
-
-extern "C" int c2d_obs_set_result(c2d_ctx* c, int32_t id, double* F, double* F2, double* count) {
-  if (!c) return C2D_E_ARG;
-  if (id < 0 || id >= c->oset.n) return fail(c, C2D_E_ARG, "c2d_obs_set_result: no member %d", (int)id);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  const ObsSetMember& M = c->oset.m[id];
-  const size_t nh = (size_t)M.n_t * M.n_mu * M.n_e;
-  if (F) HIPCHK(c, hipMemcpy(F, M.F, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (F2) HIPCHK(c, hipMemcpy(F2, M.F2, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (count) HIPCHK(c, hipMemcpy(count, M.cnt, nh * sizeof(double), hipMemcpyDeviceToHost));
-  return C2D_OK;
-}
-
-extern "C" int c2d_obs_set_kernel_ms(c2d_ctx* c, double* ms, int32_t* launches) {
-  if (!c) return C2D_E_ARG;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  if (ms) *ms = c->oset_ms;
-  if (launches) *launches = c->oset_launches;
-  return C2D_OK;
-}
-
-/* the tool's files of one deck member from its histogram so far; world_sum:
- * summed over the context's communicator first (every rank calls, rank 0
- * writes) */
-extern "C" int c2d_obs_set_write(c2d_ctx* c, int32_t id, const char* path, int32_t factor, int32_t world_sum) {
-  if (!c) return C2D_E_ARG;
-  if (id < 0 || id >= c->oset.n) return fail(c, C2D_E_ARG, "c2d_obs_set_write: no member %d", (int)id);
-  const ObsSetHost& H = c->oset_h[(size_t)id];
-  if (!H.kind) return fail(c, C2D_E_STATE, "c2d_obs_set_write: member %d was added without a deck", (int)id);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  const ObsSetMember& M = c->oset.m[id];
-  const size_t nh = (size_t)M.n_t * M.n_mu * M.n_e;
-  std::vector<double> h(3 * nh);
-  if (world_sum) {
-    if (!c->comm) return fail(c, C2D_E_STATE, "c2d_obs_set_write: world_sum needs c2d_comm_init");
-    double* w = H.red;
-    HIPCHK(c, hipMemcpyAsync(w, H.hist, 3 * nh * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    const ncclResult_t r = ncclAllReduce(w, w, 3 * nh, ncclDouble, ncclSum, c->comm, c->stream);
-    if (r != ncclSuccess) return fail(c, C2D_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
-    HIPCHK(c, hipMemcpyAsync(h.data(), w, 3 * nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->comm_rank != 0) return C2D_OK;
-  } else {
-    HIPCHK(c, hipMemcpy(h.data(), H.hist, 3 * nh * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  const double *F = h.data(), *F2 = F + nh, *cnt = F2 + nh;
-  if (H.kind == 1) {
-    const char* out = (path && path[0]) ? path : H.pspt.outfile;
-    if (c2d_pspt_write(out, &H.pspt, F, cnt, factor))
-      return fail(c, C2D_E_IO, "c2d_obs_set_write: cannot write '%s'", out);
-  } else {
-    const char* dir = (path && path[0]) ? path : ".";
-    if (c2d_plcm_write(dir, &H.plcm[0], F, F2, cnt, factor))
-      return fail(c, C2D_E_IO, "c2d_obs_set_write: cannot write the light-curve files under '%s'", dir);
-  }
-  return C2D_OK;
-}
-
-/* ------------------------------------------------------------------ */
 /* RCCL tally all-reduce (xec_add/graphics_collect, src/xec2d.f:325-399; */
 /* cens_add_up/E_add_up, src/update2d.f:1929-2078)                      */
 /* ------------------------------------------------------------------ */
@@ -3420,7 +2591,7 @@ static int file_fail(c2d_ctx* c, int rc, const char* err) {
   return rc ? (err[0] ? fail(c, rc, "%s", err) : rc) : C2D_OK;
 }
 
-static int events_parse(c2d_ctx* c, const char* path, c2d_evr_sink sink, void* user, int64_t* n) {
+int events_parse(c2d_ctx* c, const char* path, c2d_evr_sink sink, void* user, int64_t* n) {
   char err[768] = "";
   int64_t got = 0;
   const int rc = c2d_evparse_file(&c->evr, c->cfg.device, c->stream, path, sink, user, &got, &c->evr_times, err,
@@ -3463,33 +2634,6 @@ extern "C" int c2d_events_read(c2d_ctx* c, const char* path, double* buf, int64_
   HIPCHK(c, hipSetDevice(c->cfg.device));
   EvReadDst d = {c, buf, cap, 0, on_device != 0};
   return events_parse(c, path, cap > 0 ? events_read_sink : nullptr, &d, n);
-}
-
-static int obs_file_sink(void* user, const double* ev, int64_t n, int on_device) {
-  c2d_ctx* c = static_cast<c2d_ctx*>(user);
-  return on_device ? obs_launch(c, ev, n) : c2d_obs_accumulate(c, ev, n);
-}
-
-extern "C" int c2d_obs_accumulate_file(c2d_ctx* c, const char* path, int64_t* n) {
-  if (!c || !path || !path[0]) return C2D_E_ARG;
-  if (!c->obs_ready) return fail(c, C2D_E_STATE, "c2d_obs_begin must precede c2d_obs_accumulate_file");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  return events_parse(c, path, obs_file_sink, c, n);
-}
-
-static int obs_set_file_sink(void* user, const double* ev, int64_t n, int on_device) {
-  c2d_ctx* c = static_cast<c2d_ctx*>(user);
-  return on_device ? obs_set_launch_sync(c, &ev, &n, 1) : c2d_obs_set_accumulate(c, ev, n);
-}
-
-extern "C" int c2d_obs_set_accumulate_file(c2d_ctx* c, const char* path, int64_t* n) {
-  if (!c || !path || !path[0]) return C2D_E_ARG;
-  if (c->oset.n < 1) return fail(c, C2D_E_STATE, "c2d_obs_set_accumulate_file: the set is empty");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  { const int rc = obs_settle(c); if (rc) return rc; }
-  c->oset_started = true;
-  return events_parse(c, path, obs_set_file_sink, c, n);
 }
 
 extern "C" int c2d_last_events_read_ms(c2d_ctx* c, double* io_ms, double* wait_ms, double* kernel_ms,

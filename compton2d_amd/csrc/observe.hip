@@ -88,213 +88,215 @@ struct ObsSegs {
   int32_t nseg;
 };
 
+/* ---- event fetch: the segment table in LDS, then one event's words ---- */
+struct alignas(16) ObsSegsLds {            /* 528 B of the 1 KiB the host plans keep for static LDS */
+  int64_t pre[C2D_EV_SHARDS + 1];
+  const double* base[C2D_EV_SHARDS];
+};
+
+/* before the kernel's first __syncthreads */
+__device__ __forceinline__ void obs_stage_segs(ObsSegsLds& L, const ObsSegs& S) {
+  if (threadIdx.x <= (unsigned)S.nseg) L.pre[threadIdx.x] = S.pre[threadIdx.x];
+  if (threadIdx.x < (unsigned)S.nseg) L.base[threadIdx.x] = S.base[threadIdx.x];
+}
+
+/* n doubles from global memory into LDS, by the whole workgroup; dst + n */
+__device__ __forceinline__ double* obs_stage(double* dst, const double* src, int n) {
+  for (int i = threadIdx.x; i < n; i += OBS_BLOCK) dst[i] = src[i];
+  return dst + n;
+}
+
+/* what every observer needs of an event, computed once */
+struct ObsEvent {
+  double t_bound, E, ew, z;
+  double mu_c;                             /* -wmu */
+  double rcos;                             /* r cos(phi) */
+};
+
+__device__ __forceinline__ ObsEvent obs_fetch(const ObsSegsLds& L, int nseg, int64_t ee) {
+  int sg = 0;                              /* last segment with pre[sg] <= ee */
+  for (int hi = nseg - 1; sg < hi;) {
+    const int m = (sg + hi + 1) >> 1;
+    if (L.pre[m] <= ee) sg = m; else hi = m - 1;
+  }
+  const double* v = L.base[sg] + (ee - L.pre[sg]) * C2D_EVENT_WORDS;
+  ObsEvent ev;
+  ev.t_bound = v[0]; ev.E = v[1]; ev.ew = v[2];
+  const double r = v[3];
+  ev.z = v[4];
+  ev.mu_c = -v[5];
+  ev.rcos = r * c2d_cos(v[6]);
+  return ev;
+}
+
+/* One histogram as a lane sees it: the single observer's (ObsDev) or a set
+ * member's (ObsSetMember).  Edges and the privatised leading rows are in LDS;
+ * bins h = row * n_mu * n_e + col with row = time bin, and h < nl lives in LDS. */
+struct ObsView {
+  double G, betta, rmax, t_offset;
+  int32_t mode, n_t, n_mu, n_e;
+  int32_t sorted_t, sorted_mu, sorted_e;
+  const double *t0, *t1, *mu0, *mu1, *E0, *E1;   /* LDS */
+  double *hF, *hF2, *hC;                         /* LDS: nl bins each */
+  int nl;
+  double *F, *F2, *cnt;                          /* global */
+};
+
+template <class D>
+__device__ __forceinline__ ObsView obs_view(const D& d, double betta, double* edges, double* hist) {
+  ObsView V;
+  V.G = d.gam_bulk; V.betta = betta; V.rmax = d.rmax; V.t_offset = d.t_offset;
+  V.mode = d.mode; V.n_t = d.n_t; V.n_mu = d.n_mu; V.n_e = d.n_e;
+  V.sorted_t = d.sorted_t; V.sorted_mu = d.sorted_mu; V.sorted_e = d.sorted_e;
+  V.t0 = edges; V.t1 = V.t0 + d.n_t;
+  V.mu0 = V.t1 + d.n_t; V.mu1 = V.mu0 + d.n_mu;
+  V.E0 = V.mu1 + d.n_mu; V.E1 = V.E0 + d.n_e;
+  V.nl = d.lds_rows * d.n_mu * d.n_e;
+  V.hF = hist; V.hF2 = V.hF + V.nl; V.hC = V.hF2 + V.nl;
+  V.F = d.F; V.F2 = d.F2; V.cnt = d.cnt;
+  return V;
+}
+
+/* LDS bins: plain per-lane LDS atomics; the rest: wave-aggregated global
+ * atomics.  Every lane of the wave calls it (h = -1: nothing to add). */
+__device__ __forceinline__ void obs_add(const ObsView& V, int h, double w) {
+  if (h >= 0 && h < V.nl) {
+    atomicAdd(&V.hF[h], w);
+    atomicAdd(&V.hF2[h], w * w);
+    atomicAdd(&V.hC[h], 1.0);
+  }
+  agg_add(V.F, V.F2, V.cnt, h >= V.nl ? h : -1, w);
+}
+
+/* Boost, light-travel time, bin decision and add of one event in one
+ * histogram.  Wave-uniform control flow down to agg_add: no early return for
+ * an event past the end (!valid) or outside the window, they carry h = -1. */
+__device__ __forceinline__ void obs_bin_event(const ObsView& V, const ObsEvent& ev, bool valid) {
+  /* pspt.c:253-272 / plcm.c:390-399 */
+  const double G = V.G, betta = V.betta;
+  double mu = ev.mu_c;
+  const double doppler = G * (1. + mu * betta);
+  const double t_bound = (ev.t_bound - betta * ev.z * 3.33333333e-11) / doppler;
+  const double E = ev.E * doppler;
+  const double ew = ev.ew * doppler;
+  mu = (mu + betta) / (1. + mu * betta);
+  const double cdt = ev.z * mu / G + __builtin_sqrt(1. - mu * mu) * (V.rmax - ev.rcos);
+  double time = t_bound + 3.33333333e-11 * cdt;
+  if (V.mode == C2D_OBS_SED) {
+    int h = -1;
+    if (valid && !(mu < V.mu0[0] || mu > V.mu1[0])) {          /* pspt.c:274 */
+      const int k = first_bin(V.E0, V.E1, V.n_e, V.sorted_e, E);
+      const int m = first_bin(V.t0, V.t1, V.n_t, V.sorted_t, time);
+      if (k < V.n_e && m < V.n_t) h = m * V.n_e + k;
+    }
+    obs_add(V, h, ew);
+  } else {
+    time -= V.t_offset;                                        /* plcm.c:407-408 */
+    int row = -1;
+    if (valid && !(time < 0.)) {
+      const int k = first_bin(V.t0, V.t1, V.n_t, V.sorted_t, time);
+      const int m = first_bin(V.mu0, V.mu1, V.n_mu, V.sorted_mu, mu);
+      if (k < V.n_t && m < V.n_mu) row = (k * V.n_mu + m) * V.n_e;
+    }
+    for (int l = 0; l < V.n_e; l++)                            /* every band containing E */
+      obs_add(V, (row >= 0 && E >= V.E0[l] && E < V.E1[l]) ? row + l : -1, ew);
+  }
+}
+
+/* the workgroup's non-zero LDS bins to global memory (after a __syncthreads) */
+__device__ __forceinline__ void obs_flush(const ObsView& V) {
+  for (int i = threadIdx.x; i < V.nl; i += OBS_BLOCK) {
+    if (V.hC[i] != 0.0) {
+      atomicAdd(&V.F[i], V.hF[i]);
+      atomicAdd(&V.F2[i], V.hF2[i]);
+      atomicAdd(&V.cnt[i], V.hC[i]);
+    }
+  }
+}
+
+/* The single observer.  LDS: its edges, then as many leading time rows as
+ * the host found room for, up to the device's limit (obs_api.cpp
+ * obs_one_plan); beta is computed per thread. */
 __global__ void __launch_bounds__(OBS_BLOCK) c2d_obs_kernel(const ObsDev O, const ObsSegs S) {
-  __shared__ int64_t seg_pre[C2D_EV_SHARDS + 1];
-  __shared__ const double* seg_base[C2D_EV_SHARDS];
-  if (threadIdx.x <= (unsigned)S.nseg) seg_pre[threadIdx.x] = S.pre[threadIdx.x];
-  if (threadIdx.x < (unsigned)S.nseg) seg_base[threadIdx.x] = S.base[threadIdx.x];
+  __shared__ ObsSegsLds L;
+  obs_stage_segs(L, S);
   const int64_t n = S.pre[S.nseg];
   extern __shared__ double sh[];
-  double* t0 = sh;
-  double* t1 = t0 + O.n_t;
-  double* mu0 = t1 + O.n_t;
-  double* mu1 = mu0 + O.n_mu;
-  double* E0 = mu1 + O.n_mu;
-  double* E1 = E0 + O.n_e;
-  /* bins h = row * row_len + col, row = time bin; rows < lds_rows live in LDS */
-  const int row_len = O.n_mu * O.n_e;
-  const int nl = O.lds_rows * row_len;
-  double* hF = E1 + O.n_e;
-  double* hF2 = hF + nl;
-  double* hC = hF2 + nl;
-  for (int i = threadIdx.x; i < O.n_t; i += OBS_BLOCK) { t0[i] = O.t0[i]; t1[i] = O.t1[i]; }
-  for (int i = threadIdx.x; i < O.n_mu; i += OBS_BLOCK) { mu0[i] = O.mu0[i]; mu1[i] = O.mu1[i]; }
-  for (int i = threadIdx.x; i < O.n_e; i += OBS_BLOCK) { E0[i] = O.E0[i]; E1[i] = O.E1[i]; }
-  for (int i = threadIdx.x; i < 3 * nl; i += OBS_BLOCK) hF[i] = 0.0;
-  __syncthreads();
-  /* LDS bins: plain per-lane LDS atomics; the rest: wave-aggregated global atomics */
-  auto add = [&](int h, double w) {
-    if (h >= 0 && h < nl) {
-      atomicAdd(&hF[h], w);
-      atomicAdd(&hF2[h], w * w);
-      atomicAdd(&hC[h], 1.0);
-    }
-    agg_add(O.F, O.F2, O.cnt, h >= nl ? h : -1, w);
-  };
+  double* p = sh;                          /* t0 t1 mu0 mu1 E0 E1, then the rows */
+  p = obs_stage(p, O.t0, O.n_t); p = obs_stage(p, O.t1, O.n_t);
+  p = obs_stage(p, O.mu0, O.n_mu); p = obs_stage(p, O.mu1, O.n_mu);
+  p = obs_stage(p, O.E0, O.n_e); p = obs_stage(p, O.E1, O.n_e);
   const double G = O.gam_bulk;
-  const double betta = __builtin_sqrt(1. - 1. / (G * G));
+  const ObsView V = obs_view(O, __builtin_sqrt(1. - 1. / (G * G)), sh, p);
+  for (int i = threadIdx.x; i < 3 * V.nl; i += OBS_BLOCK) V.hF[i] = 0.0;
+  __syncthreads();
   /* wave-uniform trip count so the aggregation's cross-lane ops see the whole wave */
   for (int64_t base = (int64_t)blockIdx.x * OBS_BLOCK; base < n; base += (int64_t)gridDim.x * OBS_BLOCK) {
     const int64_t e = base + threadIdx.x;
     const bool valid = e < n;
-    const int64_t ee = valid ? e : 0;
-    int sg = 0;                            /* last segment with seg_pre[sg] <= ee */
-    for (int hi = S.nseg - 1; sg < hi;) {
-      const int m = (sg + hi + 1) >> 1;
-      if (seg_pre[m] <= ee) sg = m; else hi = m - 1;
-    }
-    const double* v = seg_base[sg] + (ee - seg_pre[sg]) * C2D_EVENT_WORDS;
-    double t_bound = v[0], E = v[1], ew = v[2];
-    const double r = v[3], z = v[4];
-    double mu = v[5];
-    const double phi = v[6];
-    /* pspt.c:253-272 / plcm.c:390-399 */
-    mu = -mu;
-    const double doppler = G * (1. + mu * betta);
-    t_bound = (t_bound - betta * z * 3.33333333e-11) / doppler;
-    E = E * doppler;
-    ew = ew * doppler;
-    mu = (mu + betta) / (1. + mu * betta);
-    const double cdt = z * mu / G + __builtin_sqrt(1. - mu * mu) * (O.rmax - r * c2d_cos(phi));
-    double time = t_bound + 3.33333333e-11 * cdt;
-    if (O.mode == C2D_OBS_SED) {
-      int h = -1;
-      if (valid && !(mu < mu0[0] || mu > mu1[0])) {            /* pspt.c:274 */
-        const int k = first_bin(E0, E1, O.n_e, O.sorted_e, E);
-        const int m = first_bin(t0, t1, O.n_t, O.sorted_t, time);
-        if (k < O.n_e && m < O.n_t) h = m * O.n_e + k;
-      }
-      add(h, ew);
-    } else {
-      time -= O.t_offset;                                      /* plcm.c:407-408 */
-      int row = -1;
-      if (valid && !(time < 0.)) {
-        const int k = first_bin(t0, t1, O.n_t, O.sorted_t, time);
-        const int m = first_bin(mu0, mu1, O.n_mu, O.sorted_mu, mu);
-        if (k < O.n_t && m < O.n_mu) row = (k * O.n_mu + m) * O.n_e;
-      }
-      for (int l = 0; l < O.n_e; l++)                          /* every band containing E */
-        add((row >= 0 && E >= E0[l] && E < E1[l]) ? row + l : -1, ew);
-    }
+    obs_bin_event(V, obs_fetch(L, S.nseg, valid ? e : 0), valid);
   }
-  if (nl) {
+  if (V.nl) {
     __syncthreads();
-    for (int i = threadIdx.x; i < nl; i += OBS_BLOCK) {
-      if (hC[i] != 0.0) {
-        atomicAdd(&O.F[i], hF[i]);
-        atomicAdd(&O.F2[i], hF2[i]);
-        atomicAdd(&O.cnt[i], hC[i]);
-      }
-    }
+    obs_flush(V);
   }
 }
 
 /* An observer set: up to OBS_SET_MAX binnings (SEDs and light curves, each
  * with its own Gamma, r_max, t_offset and edges) filled in one pass over the
- * events.  Per event, once: the segment lookup, the 7 words and c2d_cos(phi).
- * Per member, in a wave-uniform loop: the boost, the bin search and the
- * accumulation of c2d_obs_kernel, operation for operation, so a member's
- * bin decisions are those of the single-observer kernel.
+ * events.  Per event, once: obs_fetch.  Per member, in a wave-uniform loop:
+ * obs_bin_event, the single observer's own code, so a member's bin decisions
+ * are those of c2d_obs_kernel.
  *
- * LDS (planned on the host, capi.cpp obs_set_plan; never more than
+ * LDS (planned on the host, obs_api.cpp obs_set_plan; never more than
  * OBS_SET_LDS with the static tables): the edges of every member, then each
  * member's leading lds_rows time rows privatised (F, F2, count); later rows
- * go through agg_add to global memory. */
+ * go through agg_add to global memory.  beta per member comes from LDS. */
 __global__ void __launch_bounds__(OBS_BLOCK) c2d_obs_set_kernel(const ObsSetDev Q, const ObsSegs S) {
-  __shared__ int64_t seg_pre[C2D_EV_SHARDS + 1];
-  __shared__ const double* seg_base[C2D_EV_SHARDS];
+  __shared__ ObsSegsLds L;
   __shared__ double betta_m[OBS_SET_MAX];
-  if (threadIdx.x <= (unsigned)S.nseg) seg_pre[threadIdx.x] = S.pre[threadIdx.x];
-  if (threadIdx.x < (unsigned)S.nseg) seg_base[threadIdx.x] = S.base[threadIdx.x];
+  obs_stage_segs(L, S);
   if (threadIdx.x < (unsigned)Q.n) {
     const double G = Q.m[threadIdx.x].gam_bulk;
     betta_m[threadIdx.x] = __builtin_sqrt(1. - 1. / (G * G));
   }
   const int64_t n = S.pre[S.nseg];
   extern __shared__ double sh[];
-  for (int i = threadIdx.x; i < Q.n_edges; i += OBS_BLOCK) sh[i] = Q.edges[i];
+  obs_stage(sh, Q.edges, Q.n_edges);
   for (int i = threadIdx.x; i < Q.n_hist; i += OBS_BLOCK) sh[Q.n_edges + i] = 0.0;
   __syncthreads();
   /* wave-uniform trip counts (events, members, bands): every lane reaches agg_add */
   for (int64_t base = (int64_t)blockIdx.x * OBS_BLOCK; base < n; base += (int64_t)gridDim.x * OBS_BLOCK) {
     const int64_t e = base + threadIdx.x;
     const bool valid = e < n;
-    const int64_t ee = valid ? e : 0;
-    int sg = 0;                            /* last segment with seg_pre[sg] <= ee */
-    for (int hi = S.nseg - 1; sg < hi;) {
-      const int m = (sg + hi + 1) >> 1;
-      if (seg_pre[m] <= ee) sg = m; else hi = m - 1;
-    }
-    const double* v = seg_base[sg] + (ee - seg_pre[sg]) * C2D_EVENT_WORDS;
-    const double tb0 = v[0], En0 = v[1], ew0 = v[2];
-    const double r = v[3], z = v[4];
-    const double mu_c = -v[5];
-    const double rcos = r * c2d_cos(v[6]);
-    for (int j = 0; j < Q.n; j++) {
-      const ObsSetMember& M = Q.m[j];
-      const double* t0 = sh + M.edge_off;
-      const double* t1 = t0 + M.n_t;
-      const double* mu0 = t1 + M.n_t;
-      const double* mu1 = mu0 + M.n_mu;
-      const double* E0 = mu1 + M.n_mu;
-      const double* E1 = E0 + M.n_e;
-      const int nl = M.lds_rows * M.n_mu * M.n_e;
-      double* hF = sh + M.hist_off;
-      double* hF2 = hF + nl;
-      double* hC = hF2 + nl;
-      auto add = [&](int h, double w) {
-        if (h >= 0 && h < nl) {
-          atomicAdd(&hF[h], w);
-          atomicAdd(&hF2[h], w * w);
-          atomicAdd(&hC[h], 1.0);
-        }
-        agg_add(M.F, M.F2, M.cnt, h >= nl ? h : -1, w);
-      };
-      /* pspt.c:253-272 / plcm.c:390-399, as c2d_obs_kernel */
-      const double G = M.gam_bulk;
-      const double betta = betta_m[j];
-      double mu = mu_c;
-      const double doppler = G * (1. + mu * betta);
-      const double t_bound = (tb0 - betta * z * 3.33333333e-11) / doppler;
-      const double E = En0 * doppler;
-      const double ew = ew0 * doppler;
-      mu = (mu + betta) / (1. + mu * betta);
-      const double cdt = z * mu / G + __builtin_sqrt(1. - mu * mu) * (M.rmax - rcos);
-      double time = t_bound + 3.33333333e-11 * cdt;
-      if (M.mode == C2D_OBS_SED) {
-        int h = -1;
-        if (valid && !(mu < mu0[0] || mu > mu1[0])) {
-          const int k = first_bin(E0, E1, M.n_e, M.sorted_e, E);
-          const int m = first_bin(t0, t1, M.n_t, M.sorted_t, time);
-          if (k < M.n_e && m < M.n_t) h = m * M.n_e + k;
-        }
-        add(h, ew);
-      } else {
-        time -= M.t_offset;
-        int row = -1;
-        if (valid && !(time < 0.)) {
-          const int k = first_bin(t0, t1, M.n_t, M.sorted_t, time);
-          const int m = first_bin(mu0, mu1, M.n_mu, M.sorted_mu, mu);
-          if (k < M.n_t && m < M.n_mu) row = (k * M.n_mu + m) * M.n_e;
-        }
-        for (int l = 0; l < M.n_e; l++)                          /* every band containing E */
-          add((row >= 0 && E >= E0[l] && E < E1[l]) ? row + l : -1, ew);
-      }
-    }
+    const ObsEvent ev = obs_fetch(L, S.nseg, valid ? e : 0);
+    for (int j = 0; j < Q.n; j++)
+      obs_bin_event(obs_view(Q.m[j], betta_m[j], sh + Q.m[j].edge_off, sh + Q.m[j].hist_off), ev, valid);
   }
   if (Q.n_hist) {
     __syncthreads();
-    for (int j = 0; j < Q.n; j++) {
-      const ObsSetMember& M = Q.m[j];
-      const int nl = M.lds_rows * M.n_mu * M.n_e;
-      const double* hF = sh + M.hist_off;
-      const double* hF2 = hF + nl;
-      const double* hC = hF2 + nl;
-      for (int i = threadIdx.x; i < nl; i += OBS_BLOCK) {
-        if (hC[i] != 0.0) {
-          atomicAdd(&M.F[i], hF[i]);
-          atomicAdd(&M.F2[i], hF2[i]);
-          atomicAdd(&M.cnt[i], hC[i]);
-        }
-      }
-    }
+    for (int j = 0; j < Q.n; j++) obs_flush(obs_view(Q.m[j], 0.0, sh + Q.m[j].edge_off, sh + Q.m[j].hist_off));
   }
 }
 
 }  // namespace c2d
 
-/* one launch of the set kernel over nseg event segments; lds_bytes is the
- * plan's dynamic LDS (edges + privatised rows) */
+/* the launch's non-empty segments, back to back; false when there is none */
+static bool obs_segs(c2d::ObsSegs& S, const double* const* ev, const int64_t* n, int nseg) {
+  int k = 0;
+  S.pre[0] = 0;
+  for (int s = 0; s < nseg; s++) {
+    if (n[s] <= 0) continue;
+    S.base[k] = ev[s];
+    S.pre[k + 1] = S.pre[k] + n[s];
+    k++;
+  }
+  S.nseg = k;
+  return k > 0;
+}
+
+/* one launch of the set kernel over nseg event segments; its dynamic LDS is
+ * the plan's (edges + privatised rows) */
 extern "C" int c2d_launch_obs_set(const c2d::ObsSetDev* Q, const double* const* ev, const int64_t* n, int nseg,
                                   int grid, hipStream_t stream) {
   if (nseg < 1 || nseg > C2D_EV_SHARDS || Q->n < 1 || Q->n > c2d::OBS_SET_MAX) return (int)hipErrorInvalidValue;
@@ -309,16 +311,7 @@ extern "C" int c2d_launch_obs_set(const c2d::ObsSetDev* Q, const double* const* 
       return (int)hipErrorInvalidValue;
   }
   c2d::ObsSegs S;
-  int k = 0;
-  S.pre[0] = 0;
-  for (int s = 0; s < nseg; s++) {
-    if (n[s] <= 0) continue;
-    S.base[k] = ev[s];
-    S.pre[k + 1] = S.pre[k] + n[s];
-    k++;
-  }
-  if (k == 0) return 0;
-  S.nseg = k;
+  if (!obs_segs(S, ev, n, nseg)) return 0;
   hipLaunchKernelGGL(c2d::c2d_obs_set_kernel, dim3(grid), dim3(c2d::OBS_BLOCK), lds, stream, *Q, S);
   return (int)hipGetLastError();
 }
@@ -329,22 +322,14 @@ extern "C" size_t c2d_obs_lds_bytes(int n_t, int n_mu, int n_e, int lds_rows) {
 
 extern "C" int c2d_obs_block(void) { return c2d::OBS_BLOCK; }
 
-/* one launch over nseg event segments (ev[s], n[s] events each; at most
- * C2D_EV_SHARDS): the transport's event shards binned together */
+/* one launch of the single observer's kernel over nseg event segments (ev[s],
+ * n[s] events each; at most C2D_EV_SHARDS): the transport's event shards
+ * binned together */
 extern "C" int c2d_launch_obs_segs(const c2d::ObsDev* O, const double* const* ev, const int64_t* n, int nseg,
                                    int grid, hipStream_t stream) {
   if (nseg < 1 || nseg > C2D_EV_SHARDS) return (int)hipErrorInvalidValue;
   c2d::ObsSegs S;
-  int k = 0;
-  S.pre[0] = 0;
-  for (int s = 0; s < nseg; s++) {
-    if (n[s] <= 0) continue;
-    S.base[k] = ev[s];
-    S.pre[k + 1] = S.pre[k] + n[s];
-    k++;
-  }
-  if (k == 0) return 0;
-  S.nseg = k;
+  if (!obs_segs(S, ev, n, nseg)) return 0;
   const size_t lds = c2d_obs_lds_bytes(O->n_t, O->n_mu, O->n_e, O->lds_rows);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)c2d::c2d_obs_kernel,
@@ -353,9 +338,4 @@ extern "C" int c2d_launch_obs_segs(const c2d::ObsDev* O, const double* const* ev
   }
   hipLaunchKernelGGL(c2d::c2d_obs_kernel, dim3(grid), dim3(c2d::OBS_BLOCK), lds, stream, *O, S);
   return (int)hipGetLastError();
-}
-
-extern "C" int c2d_launch_obs(const c2d::ObsDev* O, const double* ev, int64_t n, int grid,
-                              hipStream_t stream) {
-  return c2d_launch_obs_segs(O, &ev, &n, 1, grid, stream);
 }

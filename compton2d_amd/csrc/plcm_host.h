@@ -8,10 +8,10 @@
  * order, so edges and files equal the Python's bit for bit and byte for
  * byte (tests/test_plcm_host.py): chained t0[k+1] = t0[k] + dt, chained
  * E0 * dE, and sqrt(F2 - F1*F1) without a fused multiply-add (contraction
- * is switched off inside the functions below; capi.cpp is built with
+ * is switched off inside the functions below; obs_api.cpp is built with
  * -ffp-contract=off as well).
  *
- * Header-only C99 that also compiles as C++ (capi.cpp); no device code. */
+ * Header-only C99 that also compiles as C++ (obs_api.cpp); no device code. */
 #ifndef C2D_PLCM_HOST_H
 #define C2D_PLCM_HOST_H
 

@@ -3,7 +3,7 @@
  * c2d_obs_write_pspt: the shim bins every step's escapes on the device with
  * pspt's own binning and writes pspt's file, so no event text is needed.
  *
- * Header-only C that also compiles as C++ (capi.cpp, and the test-only
+ * Header-only C that also compiles as C++ (obs_api.cpp, and the test-only
  * oracle stand-in oracle/c2d_standin.c); no device code. */
 #ifndef C2D_PSPT_HOST_H
 #define C2D_PSPT_HOST_H

@@ -310,3 +310,23 @@ def test_set_world_sum_of_one_rank_is_the_identity(tmp_path):
             assert (tmp_path / "own" / f).read_bytes() == (tmp_path / "world" / f).read_bytes(), f
     finally:
         e.close()
+
+
+def test_single_pspt_world_sum_of_one_rank_is_the_identity(tmp_path):
+    """c2d_obs_write_pspt reduces and writes through the set's code path: on
+    one rank world_sum changes no byte, and it needs the communicator."""
+    e = obs_engine(0)
+    try:
+        e.obs_begin_pspt(_deck("sed_wide"))
+        e.obs_accumulate(G["events"])
+        with _raises("C2D_E_STATE"):
+            e.obs_write_pspt(str(tmp_path / "world.dat"), 1, world_sum=True)   # no communicator yet
+        assert not (tmp_path / "world.dat").exists()
+        e.comm_init(Engine.comm_unique_id(), 0, 1)
+        e.obs_write_pspt(str(tmp_path / "own.dat"), 1, world_sum=False)
+        e.obs_write_pspt(str(tmp_path / "world.dat"), 1, world_sum=True)
+        own = (tmp_path / "own.dat").read_bytes()
+        assert len(own) > 0 and own == (tmp_path / "world.dat").read_bytes()
+        _same_text(own.decode(), str(G["out_sed_wide__%s" % list(G["files_sed_wide"])[0]]))
+    finally:
+        e.close()
