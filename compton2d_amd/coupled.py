@@ -4,7 +4,12 @@ Mirrors the reference's per-step sequence (src/xec2d.f:41-110 master,
 :141-193 worker) for the hot path:
 
     imcgen2d   tables + budgets       Engine.volume_em (c2d_volume_em) +
-                                      surface.volume_budget (src/imcgen2d.f:209-456)
+                                      surface.volume_budget (src/imcgen2d.f:209-456);
+                                      for a deck with external-Compton rings
+                                      (CoupledWorkload.boundary) the window's ring
+                                      budgets and seed tables, surface.step_surfaces
+                                      + surface.apply_bias (src/imcgen2d.f:111-183,
+                                      :436-437, :476-528)
     imcfield2d / imcvol2d / imcsurf2d Engine.transport_step (c2d_set_step + c2d_run_step)
     xec_add / cens_add_up             `allreduce` hook (RCCL all-reduce of the fused tallies)
     update                            Engine.fp_step (c2d_fp_step), n_field/ecens read
@@ -61,7 +66,10 @@ class CoupledRun:
         return self.device_resident and self.n > 0
 
     def step(self) -> dict:
-        """One MC step; returns per-phase wall times (s) and counters."""
+        """One MC step; returns per-phase wall times (s) and counters, and of
+        the boundary sources `window` (0-based; ntime once every window has
+        ended; None without a boundary), `ec_on` (the t0 gate),
+        `surface_packets` and `fbias` (the 10 nst cap's factor, 1 if unused)."""
         eng, wl, st = self.eng, self.wl, self.state
         ncycle, t = wl.clock(self.n)
         dt = wl.dt
@@ -75,17 +83,15 @@ class CoupledRun:
         self._last_vem = vem
         t1 = _time.perf_counter()
         nz, nr = wl.grid.nz, wl.grid.nr
-        zz, zr = np.zeros(nz), np.zeros(nr)
-        izz, izr = np.zeros(nz, np.int32), np.zeros(nr, np.int32)
+        surf, window, ec_on = self._surfaces(ncycle, t)
         tab = (None, None, None) if self.device_resident else (vem["kappa_tot"], vem["eps_tot"],
                                                                vem["eps_th"])
         si = abi.StepInputs(
             ncycle=ncycle, time=t, dt=dt, kappa_tot=tab[0], eps_tot=tab[1], eps_th=tab[2],
             f_nt=None if dev_el else st["f_nt"], Pnt=None if dev_el else st["Pnt"],
             n_e=st["n_e"], Eloss_th=vem["Eloss_th"], Eloss_tot=vem["Eloss_tot"],
-            zsurf=wl.fixed["zsurf"], ewsv=ewsv, nsv=nsv, nsurfi=izz, nsurfo=izz, ewsurfi=zz,
-            ewsurfo=zz, nsurfu=izr, nsurfl=izr, ewsurfu=zr, ewsurfl=zr, tbbi=zz, tbbo=zz,
-            tbbu=zr, tbbl=zr)
+            zsurf=wl.fixed["zsurf"], ewsv=ewsv, nsv=nsv, **surf)
+        fbias = surface.apply_bias(wl.nst, si) if wl.boundary is not None else 1.0
         eng.transport_step(si)
         if self.after_transport is not None:
             self.after_transport()
@@ -128,7 +134,9 @@ class CoupledRun:
             all_paths=float(all_paths), sources=float(c[abi.CNT_SOURCES]),
             census=float(c[abi.CNT_CENSUS]), escapes=float(c[abi.CNT_ESCAPES]),
             aborted=float(c[abi.CNT_ABORTED]), mean_Te=float(np.mean(st.get("Te_new", st["tea"]))),
-            volume_packets=int(nsv.sum()))
+            volume_packets=int(np.sum(si.nsv)), window=window, ec_on=ec_on,
+            surface_packets=int(np.sum(si.nsurfi) + np.sum(si.nsurfo) + np.sum(si.nsurfu)
+                                + np.sum(si.nsurfl)), fbias=fbias)
         self.n += 1
         return self.last
 
@@ -141,15 +149,29 @@ class CoupledRun:
         vin = dict(wl.fixed, tea=st["tea"], n_e=st["n_e"], f_nt=f)
         vem = self.eng.volume_em(wl.dt, vin, tables_to_host=True)
         nsv, ewsv = surface.volume_budget(wl.nst, vem["Eloss_tot"])
+        surf, _, _ = self._surfaces(ncycle, t)
+        si = abi.StepInputs(
+            ncycle=ncycle, time=t, dt=wl.dt, kappa_tot=vem["kappa_tot"], eps_tot=vem["eps_tot"],
+            eps_th=vem["eps_th"], f_nt=f, Pnt=p, n_e=st["n_e"], Eloss_th=vem["Eloss_th"],
+            Eloss_tot=vem["Eloss_tot"], zsurf=wl.fixed["zsurf"], ewsv=ewsv, nsv=nsv, **surf)
+        if wl.boundary is not None:
+            surface.apply_bias(wl.nst, si)
+        return si
+
+    def _surfaces(self, ncycle: int, t: float):
+        """(surface fields of the step's StepInputs, window, ec_on): the
+        deck's boundary rings in the window of this step
+        (surface.step_surfaces), or no surface sources at all for a workload
+        without a boundary."""
+        wl = self.wl
+        b = wl.boundary
+        if b is not None:
+            return surface.step_surfaces(b, b.r, b.rmin, wl.nst, ncycle, t, wl.dt)
         nz, nr = wl.grid.nz, wl.grid.nr
         zz, zr = np.zeros(nz), np.zeros(nr)
         izz, izr = np.zeros(nz, np.int32), np.zeros(nr, np.int32)
-        return abi.StepInputs(
-            ncycle=ncycle, time=t, dt=wl.dt, kappa_tot=vem["kappa_tot"], eps_tot=vem["eps_tot"],
-            eps_th=vem["eps_th"], f_nt=f, Pnt=p, n_e=st["n_e"], Eloss_th=vem["Eloss_th"],
-            Eloss_tot=vem["Eloss_tot"], zsurf=wl.fixed["zsurf"], ewsv=ewsv, nsv=nsv, nsurfi=izz,
-            nsurfo=izz, ewsurfi=zz, ewsurfo=zz, nsurfu=izr, nsurfl=izr, ewsurfu=zr, ewsurfl=zr,
-            tbbi=zz, tbbo=zz, tbbu=zr, tbbl=zr)
+        return dict(nsurfi=izz, nsurfo=izz, ewsurfi=zz, ewsurfo=zz, nsurfu=izr, nsurfl=izr,
+                    ewsurfu=zr, ewsurfl=zr, tbbi=zz, tbbo=zz, tbbu=zr, tbbl=zr), None, False
 
     @staticmethod
     def sample_step(si: abi.StepInputs, frac: float) -> abi.StepInputs:

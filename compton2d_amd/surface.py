@@ -16,6 +16,9 @@ the `SpectrumTable` that `c2d_set_step` uploads; the sampling itself
   `nsurfl`), :476-485 (`ewsurfu`, `ewsurfl`), :499-528 (bias cap); ring areas
   src/setup2d.f:102-113.
 * volume budget  src/imcgen2d.f:406-413 (`Emiss_tot`), :446-456 (`nsv`, `ewsv`).
+* `step_surfaces` composes these for one step of a deck's boundary
+  (`Boundary`, built by deck.deck_workload): what coupled.CoupledRun hands to
+  the transport.
 
 Arithmetic follows the reference's expression order with `math` (glibc) so the
 tables equal the reference's bit for bit (tests/test_surface.py pins them
@@ -213,6 +216,77 @@ def volume_budget(nst: int, fas: np.ndarray):
     pos = nsv > 0
     ewsv[pos] = fas[pos] / nsv[pos].astype(np.float64)
     return nsv, ewsv
+
+
+@dataclass
+class Boundary:
+    """The boundary sources of a run, as its deck states them: per window
+    [ntime] the gate time t0 and the end t1, per window and ring [ntime, nr]
+    the temperatures and the index of the ring's seed table in `tables`
+    (-1: the ring has none), the `file_sp` tables with their integrals, one
+    per distinct file, and the ring geometry.  Nothing here depends on nst or
+    on the step (deck.deck_workload builds it, step_surfaces reads it)."""
+    nz: int
+    r: np.ndarray
+    rmin: float
+    t0: np.ndarray
+    t1: np.ndarray
+    tbbu: np.ndarray
+    tbbl: np.ndarray
+    spec_u: np.ndarray
+    spec_l: np.ndarray
+    files: list
+    tables: list
+    int_file: list
+
+
+def _side_budget(r, rmin, nst, dt, tbb, spec, ec_on, int_file):
+    """ring_budget of one side whose rings may name different files: a ring's
+    energy takes the integral of its own table (imcgen2d calls file_sp per ring)."""
+    nsurf, ewsurf, _ = ring_budget(r, rmin, nst, dt, tbb, ec_on, 0.0)
+    for m in sorted(set(int(s) for s in spec if s >= 0)):
+        n_m, ew_m, _ = ring_budget(r, rmin, nst, dt, tbb, ec_on, int_file[m])
+        nsurf[spec == m], ewsurf[spec == m] = n_m[spec == m], ew_m[spec == m]
+    return nsurf, ewsurf
+
+
+def step_surfaces(boundary: Boundary, r: np.ndarray, rmin: float, nst: int, ncycle: int,
+                  time: float, dt: float):
+    """(fields, window, ec_on) of one MC step: `fields` holds the surface
+    fields of abi.StepInputs (nsurf*, ewsurf*, tbb*, spectra, spec_*) before
+    the bias cap (apply_bias), `window` the 0-based window of time_window
+    (src/imcgen2d.f:111-120) and `ec_on` the gate time + dt/2 >= t0[window]
+    (:127, :156, :174).  The upper and lower rings get ring_budget with the
+    integral of their own file; the inner and outer z-surfaces have no
+    sources (src/reader.f:249-251).
+
+    Two cases the reference leaves open:
+
+    * No window.  When every t1 lies behind time + dt/2 the reference's loop
+      leaves t = ntime + 1 and indexes past its arrays.  Here there are no
+      boundary sources then: window = ntime, ec_on False, all fields zero.
+    * A tbb < 0 ring while the gate is closed.  As in the reference it gets
+      the blackbody energy of |tbb| (ring_budget with ec_on False) and its
+      packets.  They draw from the ring's own file table; the reference
+      samples whatever the last file_sp call left in COMMON, which before
+      the first open gate is an unset table."""
+    b = boundary
+    nr = len(r)
+    w = time_window(ncycle, time, dt, b.t1)
+    zz, izz, none_z = np.zeros(b.nz), np.zeros(b.nz, np.int32), np.full(b.nz, -1, np.int32)
+    f = dict(nsurfi=izz, nsurfo=izz, ewsurfi=zz, ewsurfo=zz, tbbi=zz, tbbo=zz,
+             spec_i=none_z, spec_o=none_z, spectra=list(b.tables))
+    if w >= len(b.t1):
+        f.update(nsurfu=np.zeros(nr, np.int32), nsurfl=np.zeros(nr, np.int32), ewsurfu=np.zeros(nr),
+                 ewsurfl=np.zeros(nr), tbbu=np.zeros(nr), tbbl=np.zeros(nr),
+                 spec_u=np.full(nr, -1, np.int32), spec_l=np.full(nr, -1, np.int32))
+        return f, w, False
+    ec_on = bool(time + 0.5 * dt >= b.t0[w])
+    f["nsurfu"], f["ewsurfu"] = _side_budget(r, rmin, nst, dt, b.tbbu[w], b.spec_u[w], ec_on, b.int_file)
+    f["nsurfl"], f["ewsurfl"] = _side_budget(r, rmin, nst, dt, b.tbbl[w], b.spec_l[w], ec_on, b.int_file)
+    f.update(tbbu=b.tbbu[w].copy(), tbbl=b.tbbl[w].copy(), spec_u=b.spec_u[w].copy(),
+             spec_l=b.spec_l[w].copy())
+    return f, w, ec_on
 
 
 def apply_bias(nst: int, step: abi.StepInputs) -> float:

@@ -196,13 +196,16 @@ def c2_workload(nz: int = 32, nr: int = 32, sources: int = 10_000_000, splits=(1
 
 class CoupledWorkload:
     """A T_const = 0 run: grid, deck, the initial zone state and what stays
-    fixed per zone (the imcgen2d / update inputs of src/xec2d.f:67-87)."""
+    fixed per zone (the imcgen2d / update inputs of src/xec2d.f:67-87).
+    `boundary`: the surface.Boundary of a deck with external-Compton rings
+    (deck.deck_workload), None for a run without boundary sources."""
 
     def __init__(self, grid: abi.GridConfig, deck: dict, nst: int, dt: float, state0: dict,
-                 fixed: dict, fp_const: abi.FpConstants, description: str):
+                 fixed: dict, fp_const: abi.FpConstants, description: str, boundary=None):
         self.grid, self.deck, self.nst, self.dt = grid, deck, nst, dt
         self.state0, self.fixed, self.fp_const = state0, fixed, fp_const
         self.description = description
+        self.boundary = boundary
 
     def clock(self, n: int):
         return n, max(n - 1, 0) * self.dt
