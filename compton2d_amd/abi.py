@@ -674,3 +674,15 @@ class CkptInfo(C.Structure):
         ("sections", _i32), ("fp_auto_known", _i32), ("fp_auto_exact", _i32), ("reserved", _i32),
         ("grid_digest", C.c_uint64), ("seed", C.c_uint64), ("time", _d), ("dt", _d),
         ("n_records", _i64), ("chunk", _i64), ("user_bytes", _i64), ("file_bytes", _i64)]
+
+
+# ---- census population control (c2d_census_stats / c2d_census_roulette) ----
+ROULETTE_GROUPS_MAX = 32            # C2D_ROULETTE_GROUPS_MAX
+ROULETTE_NSP = NPHOMAX + 1          # entries of group_of_sp (jgpsp 0..NPHOMAX)
+TAG_ROULETTE = 0x0C                 # C2D_TAG_ROULETTE (csrc/c2d_rng.h)
+
+
+class RouletteOut(C.Structure):
+    """c2d_roulette_out: what one c2d_census_roulette pass did."""
+    _fields_ = [("n_before", _i64), ("n_after", _i64), ("n_tested", _i64),
+                ("e_before", _d), ("e_after", _d), ("kernel_ms", _d)]

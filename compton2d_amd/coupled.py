@@ -14,6 +14,10 @@ Mirrors the reference's per-step sequence (src/xec2d.f:41-110 master,
     xec_add / cens_add_up             `allreduce` hook (RCCL all-reduce of the fused tallies)
     update                            Engine.fp_step (c2d_fp_step), n_field/ecens read
                                       from the device tallies (src/update2d.f:7-327)
+    (no counterpart: the reference    optional census population control after the
+     stops at ucens records)          update (popcontrol.CensusControl): census
+                                      statistics, the default weight floors and the
+                                      weight-window roulette on the device
 
 With `device_resident` (the default) the 400-bin emission/absorption tables
 and the 200-bin electron spectra never leave the GPU: c2d_volume_em keeps its
@@ -28,7 +32,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from . import abi, surface
+from . import abi, popcontrol, surface
 from .engine import Engine
 from .synth import CoupledWorkload
 
@@ -38,14 +42,25 @@ class CoupledRun:
 
     def __init__(self, eng: Engine, wl: CoupledWorkload, device_resident: bool = True,
                  allreduce: Optional[Callable[[], None]] = None, fp_mode: int = abi.FP_AUTO,
-                 after_transport: Optional[Callable[[], None]] = None):
+                 after_transport: Optional[Callable[[], None]] = None,
+                 census_control: Optional[popcontrol.CensusControl] = None):
         """fp_mode: the FP update's arithmetic (Engine.fp_set_mode); the
         default abi.FP_AUTO picks exact or fast per update, and each step's
         row logs what ran (`fp_mode`).  after_transport: called as soon as a
         step's transport has returned, before the tally exchange and the FP
         update (e.g. the on-device SED binning of the step's escapes, which
-        then runs on its own stream beside them)."""
+        then runs on its own stream beside them).  census_control: bound the
+        census with the weight-window roulette (popcontrol.CensusControl):
+        after a step's transport, tally exchange and FP update, when the
+        census (summed over ranks through its stats_allreduce) exceeds
+        target * (1 + slack), the floors of popcontrol.weight_floor are
+        applied with salt = ncycle, and the step's row gains census_before,
+        census_after and roulette_ms.  None (the default) changes nothing."""
         self.eng, self.wl = eng, wl
+        self.census_control = census_control
+        self._groups = None
+        if census_control is not None:
+            self._groups = census_control.groups or popcontrol.groups_by_decade(wl.grid.hu)
         self.after_transport = after_transport
         self.device_resident = device_resident
         self.allreduce = allreduce
@@ -137,6 +152,8 @@ class CoupledRun:
             volume_packets=int(np.sum(si.nsv)), window=window, ec_on=ec_on,
             surface_packets=int(np.sum(si.nsurfi) + np.sum(si.nsurfo) + np.sum(si.nsurfu)
                                 + np.sum(si.nsurfl)), fbias=fbias)
+        if self.census_control is not None:
+            self.last.update(popcontrol.apply_control(eng, self.census_control, self._groups, ncycle))
         self.n += 1
         return self.last
 

@@ -198,6 +198,11 @@ struct c2d_ctx {
   hipEvent_t cens_ev[2] = {nullptr, nullptr};
   c2d_ckpt_stage* ckpt = nullptr;           /* the checkpoint calls' staging buffers (ckpt.hip) */
   c2d_ckpt_times ckpt_times = {};           /* of the last c2d_checkpoint_write / _read */
+  /* census population control (roulette.hip): its control block, tables and
+   * statistics in one allocation */
+  unsigned char* rl_buf = nullptr;
+  size_t rl_bytes = 0;
+  float last_stats_ms = 0.f;                /* device time of the last c2d_census_stats kernel */
   bool have_kappa_prev = false;             /* a step has left its kappa table for the next (H3) */
   int64_t ev_cap_sh = 0;                /* per-shard capacity                             */
   ScatRec *q2[2] = {nullptr, nullptr}, *q3[2] = {nullptr, nullptr};

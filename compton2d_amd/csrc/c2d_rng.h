@@ -36,6 +36,9 @@
  *   its resample k   = (K_split3, sub k), counter 0 at each attempt    (imctrk2d.f:634-648,
  *                      `goto 215`); the copy flies on from its first success's stream
  *   census key       = census_key(K_pkt, ctr_pkt, sub_pkt)             (imctrk2d.f:571)
+ *   roulette key     = derive(K_census, TAG_ROULETTE, salt lo, salt hi): its draw 0
+ *                      decides a census record's survival (c2d_roulette.h); the
+ *                      record's own streams, drawn from K_census directly, are untouched
  *   compb2d's first rejection loop (compb_2d.f:59-93): iteration j draws
  *                      counters c0 + 5j .. c0 + 5j + 4 of the packet's stream (c0:
  *                      the counter at the call), the rest of compb2d follows
@@ -65,6 +68,7 @@
 #define C2D_TAG_SCAT2   0x09u
 #define C2D_TAG_SCAT3   0x0Au
 #define C2D_TAG_CENSUS  0x0Bu
+#define C2D_TAG_ROULETTE 0x0Cu  /* census population control (c2d_roulette.h) */
 
 #define C2D_DRAW_C3     0x5EEDD1CEu
 #define C2D_DERIVE_C3   0x9E3779B9u

@@ -21,6 +21,7 @@
 #include "c2d_rng.h"
 #include "reflect_host.h"
 #include "c2d_censfmt.h"
+#include "c2d_roulette.hpp"
 
 extern "C" int c2d_launch_transport_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
                                           int trk, int refl, hipStream_t s);
@@ -335,7 +336,7 @@ extern "C" void c2d_finalize(c2d_ctx* c) {
                   c->vol_prefix, c->surf_prefix, c->surf_spec, c->spectra, c->comtab, c->comS,
                   c->ev, c->q2[0], c->q2[1], c->q3[0], c->q3[1], c->T_own, c->nf_rep, c->ctl, c->derr, c->dP,
                   c->cscan, c->ctile_cnt, c->ctile_off, c->ctile_flag, c->cstate, c->clist[0], c->clist[1],
-                  c->pool, c->out_list, c->relist, c->cflag, c->part_id, c->part_off, c->tmp_rec};
+                  c->pool, c->out_list, c->relist, c->cflag, c->part_id, c->part_off, c->tmp_rec, c->rl_buf};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int b = 0; b < 2; b++) {
@@ -1833,6 +1834,179 @@ extern "C" int c2d_census_truncate(c2d_ctx* c, int64_t n) {
   c->census_lost = false;
   c->n_census = n;
   if (c->chunked) c->n_clist = (n + C2D_CCHUNK - 1) / C2D_CCHUNK;
+  return C2D_OK;
+}
+
+/* ---- census population control (c2d_roulette.h, roulette.hip) ---- */
+/* ngroup and every entry of group_of_sp in range, or C2D_E_ARG (c may be NULL: the host twin) */
+static int roulette_args(c2d_ctx* c, const char* who, const int32_t* group_of_sp, int32_t ngroup) {
+  if (ngroup < 1 || ngroup > C2D_ROULETTE_GROUPS_MAX)
+    return fail(c, C2D_E_ARG, "%s: ngroup %d outside 1..%d", who, (int)ngroup, C2D_ROULETTE_GROUPS_MAX);
+  for (int i = 0; i < C2D_ROULETTE_NSP; i++)
+    if (group_of_sp[i] < 0 || group_of_sp[i] >= ngroup)
+      return fail(c, C2D_E_ARG, "%s: group_of_sp[%d] = %d outside 0..%d", who, i, (int)group_of_sp[i],
+                  (int)ngroup - 1);
+  return C2D_OK;
+}
+
+struct RlBufs {
+  RouletteCtl* ctl;
+  int32_t* group;               /* [C2D_ROULETTE_NSP]       */
+  double* w_min;                /* [ncell * ngroup]         */
+  unsigned long long* count;    /* [ncell * ngroup] (stats) */
+  double* energy;               /* [ncell * ngroup] (stats) */
+};
+
+/* the context's roulette allocation cut for nbins (cell, group) pairs, the group table uploaded */
+static int roulette_bufs(c2d_ctx* c, const int32_t* group_of_sp, int64_t nbins, RlBufs* b) {
+  const size_t head = (sizeof(RouletteCtl) + 255) / 256 * 256, grp = 768,
+               need = head + grp + 3 * sizeof(double) * (size_t)nbins;
+  static_assert(sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "roulette buffer layout");
+  if (c->rl_bytes < need) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->rl_buf) (void)hipFree(c->rl_buf);
+    c->rl_buf = nullptr;
+    c->rl_bytes = 0;
+    HIPCHK(c, dalloc(&c->rl_buf, need));
+    c->rl_bytes = need;
+  }
+  b->ctl = reinterpret_cast<RouletteCtl*>(c->rl_buf);
+  b->group = reinterpret_cast<int32_t*>(c->rl_buf + head);
+  b->w_min = reinterpret_cast<double*>(c->rl_buf + head + grp);
+  b->count = reinterpret_cast<unsigned long long*>(b->w_min + nbins);
+  b->energy = reinterpret_cast<double*>(b->count + nbins);
+  HIPCHK(c, hipMemcpyAsync(b->group, group_of_sp, sizeof(int32_t) * C2D_ROULETTE_NSP, hipMemcpyHostToDevice,
+                           c->stream));
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_stats(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, int64_t* count,
+                                double* energy) {
+  if (!c) return C2D_E_ARG;
+  if (!group_of_sp || !count || !energy) return fail(c, C2D_E_ARG, "c2d_census_stats: a null pointer");
+  { const int rc = roulette_args(c, "c2d_census_stats", group_of_sp, ngroup); if (rc) return rc; }
+  if (c->census_lost) return census_lost(c, "c2d_census_stats");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int64_t nbins = (int64_t)c->ncell * ngroup;
+  RlBufs b;
+  { const int rc = roulette_bufs(c, group_of_sp, nbins, &b); if (rc) return rc; }
+  HIPCHK(c, hipMemsetAsync(b.count, 0, 2 * sizeof(double) * (size_t)nbins, c->stream));   /* count | energy */
+  if (!c->cens_ev[0]) HIPCHK(c, hipEventCreate(&c->cens_ev[0]));
+  if (!c->cens_ev[1]) HIPCHK(c, hipEventCreate(&c->cens_ev[1]));
+  HIPCHK(c, hipEventRecord(c->cens_ev[0], c->stream));
+  HIPCHK(c, (hipError_t)c2d_launch_census_stats(c->cens[c->cur].soa(), cens_list(c), c->n_census, c->nz, c->nr,
+                                                (int)ngroup, b.group, b.count, b.energy, c->n_cu, c->stream));
+  HIPCHK(c, hipEventRecord(c->cens_ev[1], c->stream));
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are copied as they are");
+  HIPCHK(c, hipMemcpyAsync(count, b.count, sizeof(int64_t) * (size_t)nbins, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(energy, b.energy, sizeof(double) * (size_t)nbins, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipEventElapsedTime(&c->last_stats_ms, c->cens_ev[0], c->cens_ev[1]));
+  return C2D_OK;
+}
+
+extern "C" int c2d_last_census_stats_ms(c2d_ctx* c, double* ms) {
+  if (!c || !ms) return C2D_E_ARG;
+  *ms = (double)c->last_stats_ms;
+  return C2D_OK;
+}
+
+/* the pass itself; *began = the census has been (or may have been) rewritten */
+static int roulette_body(c2d_ctx* c, const RlBufs& b, int32_t ngroup, bool any_floor, uint64_t salt,
+                         hipEvent_t e0, hipEvent_t e1, RouletteCtl* res, float* ms, bool* began) {
+  const int64_t n = c->n_census;
+  const CensusSoA cs = c->cens[c->cur].soa();
+  HIPCHK(c, hipMemsetAsync(b.ctl, 0, sizeof(RouletteCtl), c->stream));
+  int64_t S = n;
+  if (any_floor) {
+    /* the scratch: a slice's records and the slack of its RL_SHARDS regions */
+    const int rc = ensure_tmp(c, std::min<int64_t>(n, int64_t(1) << 22) + (int64_t)RL_SHARDS * RL_TILE);
+    if (rc) return rc;
+    S = rl_slice(c->tmp_cap);
+    /* test knob: short slices force many rounds on a small census */
+    if (const char* e = getenv("C2D_ROULETTE_SLICE")) S = std::max<int64_t>(1, std::min<int64_t>(S, atoll(e)));
+  }
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  *began = any_floor;
+  for (int64_t first = 0; first < n; first += S)
+    HIPCHK(c, (hipError_t)c2d_launch_roulette_slice(cs, cens_list(c), first, std::min(S, n - first), c->nz, c->nr,
+                                                    (int)ngroup, b.group, b.w_min, salt, c->tmp_rec, c->tmp_cap,
+                                                    b.ctl, any_floor ? 1 : 0, c->n_cu, c->stream));
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res, b.ctl, sizeof *res, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipEventElapsedTime(ms, e0, e1));
+  if (!any_floor) res->W = (unsigned long long)n;
+  if ((int64_t)res->W > n)
+    return fail(c, C2D_E_STATE, "c2d_census_roulette: %llu records written of %lld read", res->W, (long long)n);
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_roulette(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* w_min,
+                                   uint64_t salt, c2d_roulette_out* out) {
+  if (!c) return C2D_E_ARG;
+  if (!group_of_sp || !w_min || !out) return fail(c, C2D_E_ARG, "c2d_census_roulette: a null pointer");
+  { const int rc = roulette_args(c, "c2d_census_roulette", group_of_sp, ngroup); if (rc) return rc; }
+  if (c->census_lost) return census_lost(c, "c2d_census_roulette");
+  const c2d_roulette_out zero = {};
+  *out = zero;
+  out->n_before = out->n_after = c->n_census;
+  if (c->n_census == 0) return C2D_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int64_t nbins = (int64_t)c->ncell * ngroup;
+  /* no floor that can test a record: the census is only summed, and stays as it is, order included */
+  bool any_floor = false;
+  for (int64_t i = 0; i < nbins && !any_floor; i++) any_floor = w_min[i] > 0.0 && std::isfinite(w_min[i]);
+  RlBufs b;
+  { const int rc = roulette_bufs(c, group_of_sp, nbins, &b); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(b.w_min, w_min, sizeof(double) * (size_t)nbins, hipMemcpyHostToDevice, c->stream));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIPCHK(c, hipEventCreate(&ev[0]));
+  if (hipEventCreate(&ev[1]) != hipSuccess) {
+    (void)hipEventDestroy(ev[0]);
+    return fail(c, C2D_E_HIP, "c2d_census_roulette: hipEventCreate");
+  }
+  RouletteCtl res = {};
+  float ms = 0.f;
+  bool began = false;
+  const int rc = roulette_body(c, b, ngroup, any_floor, salt, ev[0], ev[1], &res, &ms, &began);
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  if (rc) {
+    if (began) {   /* partly rewritten: lost, as after a failed in-place step */
+      (void)hipStreamSynchronize(c->stream);
+      c->n_census = 0;
+      if (c->chunked) c->n_clist = 0;
+      c->census_lost = true;
+    }
+    return rc;
+  }
+  c->n_census = (int64_t)res.W;
+  if (c->chunked) c->n_clist = (c->n_census + C2D_CCHUNK - 1) / C2D_CCHUNK;   /* the rest is free again */
+  out->n_after = c->n_census;
+  out->n_tested = (int64_t)res.n_tested;
+  out->e_before = res.e_before;
+  out->e_after = res.e_after;
+  out->kernel_ms = (double)ms;
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_roulette_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
+                                        int32_t nz, int32_t nr, const int32_t* group_of_sp, int32_t ngroup,
+                                        const double* w_min, uint64_t salt, uint8_t* keep, double* ew_out) {
+  if (n < 0 || nz < 1 || nz > C2D_MAXZONE || nr < 1 || nr > C2D_MAXZONE || !group_of_sp || !w_min) return C2D_E_ARG;
+  if (n > 0 && (!d6 || !i5 || !keys || !keep || !ew_out)) return C2D_E_ARG;
+  if (roulette_args(nullptr, "c2d_census_roulette_host", group_of_sp, ngroup)) return C2D_E_ARG;
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t* q = i5 + 5 * i;
+    if (q[3] < 1 || q[3] > nz || q[4] < 1 || q[4] > nr || q[0] < 0 || q[0] > 255) return C2D_E_ARG;
+  }
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t* q = i5 + 5 * i;
+    const int g = group_of_sp[c2d_roulette_sp((uint32_t)q[0])];
+    const double w = w_min[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + g];
+    keep[i] = c2d_roulette_decide(d6[6 * i + 4], w, keys[i], salt, ew_out + i) != C2D_ROULETTE_REMOVED ? 1 : 0;
+  }
   return C2D_OK;
 }
 

@@ -24,6 +24,11 @@ and per-ring table indices on the workload as `boundary`
 data/medium_inputm.npz, the initial electron spectra and the IC-loss table
 come from the run-setup calls (csrc/setup.hip): gam_min + P_nontherm per zone
 and IC_loss, on the GPU or on the host.
+
+A deck says nothing about the size of the census: the reference stops at
+ucens records a rank (src/imctrk2d.f:573-577).  A long deck run on a card it
+would fill passes `coupled.CoupledRun` a `popcontrol.CensusControl`
+(`census_control=`), which bounds the census with the weight-window roulette.
 """
 from __future__ import annotations
 

@@ -131,6 +131,16 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_census_append.argtypes = [vp, C.c_void_p, C.c_int64]
     lib.c2d_census_truncate.restype = C.c_int
     lib.c2d_census_truncate.argtypes = [vp, C.c_int64]
+    lib.c2d_census_stats.restype = C.c_int
+    lib.c2d_census_stats.argtypes = [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.c2d_last_census_stats_ms.restype = C.c_int
+    lib.c2d_last_census_stats_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.c2d_census_roulette.restype = C.c_int
+    lib.c2d_census_roulette.argtypes = [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64,
+                                        C.POINTER(abi.RouletteOut)]
+    lib.c2d_census_roulette_host.restype = C.c_int
+    lib.c2d_census_roulette_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.c2d_census_import.restype = C.c_int
     lib.c2d_census_import.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_uint64), C.c_int64]
@@ -412,6 +422,47 @@ class Engine:
 
     def census_truncate(self, n: int) -> None:
         self._check(self.lib.c2d_census_truncate(self.ctx, int(n)))
+
+    # -- census population control (compton2d_amd/popcontrol.py) -------------
+    @staticmethod
+    def _group_table(group_of_sp) -> np.ndarray:
+        g = np.ascontiguousarray(group_of_sp, np.int32).reshape(-1)
+        if g.size != abi.ROULETTE_NSP:
+            raise ValueError("group_of_sp holds %d entries, %d expected" % (g.size, abi.ROULETTE_NSP))
+        return g
+
+    def census_stats(self, group_of_sp, ngroup: int):
+        """(count int64, energy f64), each [nz, nr, ngroup]: the census's
+        records and their summed ew per cell and spectral group
+        (c2d_census_stats); the census is unchanged."""
+        g = self._group_table(group_of_sp)
+        shape = (self.nz, self.nr, max(int(ngroup), 1))
+        count, energy = np.zeros(shape, np.int64), np.zeros(shape, np.float64)
+        self._check(self.lib.c2d_census_stats(self.ctx, g.ctypes.data, int(ngroup), count.ctypes.data,
+                                              energy.ctypes.data))
+        return count, energy
+
+    def last_census_stats_ms(self) -> float:
+        """Device time of the last census_stats kernel (c2d_last_census_stats_ms)."""
+        ms = C.c_double()
+        self._check(self.lib.c2d_last_census_stats_ms(self.ctx, C.byref(ms)))
+        return ms.value
+
+    def census_roulette(self, group_of_sp, ngroup: int, w_min, salt: int) -> dict:
+        """Weight-window roulette of the census against the floors w_min
+        [nz, nr, ngroup] (c2d_census_roulette; the rule: popcontrol.roulette_numpy).
+        Returns n_before, n_after, n_tested, e_before, e_after, kernel_ms."""
+        g = self._group_table(group_of_sp)
+        w = None
+        if w_min is not None:
+            w = np.ascontiguousarray(w_min, np.float64)
+            if w.size != self.nz * self.nr * int(ngroup) and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX:
+                raise ValueError("w_min holds %d floors, %d expected" % (w.size, self.nz * self.nr * int(ngroup)))
+        out = abi.RouletteOut()
+        self._check(self.lib.c2d_census_roulette(self.ctx, g.ctypes.data, int(ngroup),
+                                                 w.ctypes.data if w is not None else None,
+                                                 int(salt) & 0xFFFFFFFFFFFFFFFF, C.byref(out)))
+        return {k: getattr(out, k) for k, _ in abi.RouletteOut._fields_}
 
     def import_census(self, d6, i5, keys) -> None:
         d6 = np.ascontiguousarray(d6, np.float64)

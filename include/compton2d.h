@@ -494,6 +494,62 @@ int  c2d_census_truncate(c2d_ctx* ctx, int64_t n);
 int  c2d_census_export_range(c2d_ctx* ctx, int64_t first, int64_t stride, double* d6,
                              int32_t* i5, uint64_t* keys, int64_t cap, int64_t* n);
 
+/* Census population control: weight-window roulette on the device
+ * (csrc/c2d_roulette.h, csrc/roulette.hip).  The reference
+ * stops at ucens records a rank (imctrk2d.f:573-577) and this library returns
+ * C2D_E_CENSUS_OVERFLOW; with these calls a host bounds the census instead.
+ * Opt-in: nothing else in the library calls them.
+ *
+ * group_of_sp[C2D_NPHOMAX + 1] maps a record's spectral bin jgpsp (bits 0-7
+ * of its bins word, larger values taken as C2D_NPHOMAX) to a group
+ * 0..ngroup-1, 1 <= ngroup <= C2D_ROULETTE_GROUPS_MAX; tables are
+ * [nz][nr][ngroup], host memory.
+ *
+ * c2d_census_stats: per (cell, group) the exact record count and the sum of
+ * ew of the census, which stays as it is.
+ *
+ * c2d_census_roulette: a record in cell (jph, kph) and group g with
+ * w = w_min[jph-1][kph-1][g] is untouched if !(w > 0), if w is not finite, if
+ * !(ew >= 0) or if ew >= w.  Otherwise it survives with probability ew / w,
+ * its ew then exactly w and nothing else changed (its key included), or is
+ * removed: the expected energy is unchanged.  The decision is draw 0 of the
+ * key derived from the record's key with the tag C2D_TAG_ROULETTE and `salt`
+ * (c2d_rng.h), a function of the record, its floor and the salt alone, so it
+ * does not depend on the census mode, the record's place or the GPU; use a
+ * new salt for every pass (the step number).  The census stays a valid
+ * census in both modes, the chunks it no longer needs are free again as
+ * after c2d_census_truncate, and the order of the survivors is free; with no
+ * floor that can test a record the census is left exactly as it is.
+ * out->n_tested counts the records with ew < w; e_before and e_after are the
+ * sums of ew; kernel_ms is the device time of the pass.
+ *
+ * Errors: C2D_E_ARG, before the census is touched, for a null pointer, ngroup
+ * out of range or a group id outside 0..ngroup-1; C2D_E_STATE if the census
+ * was lost.  A HIP failure after c2d_census_roulette has begun rewriting
+ * leaves the census lost, exactly as a failed in-place step does: the count
+ * is 0 and census reads and c2d_run_step return C2D_E_STATE until the next
+ * c2d_census_import, c2d_census_read or c2d_census_truncate.
+ *
+ * c2d_census_roulette_host: the same rule on n records in the layout of
+ * c2d_census_export; keep[i] = 1 for a record that stays, ew_out[i] its ew
+ * afterwards (the floor for a survivor of a test, else ew as given).  Needs
+ * no context and no GPU; C2D_E_ARG also for a record whose cell is off the
+ * nz x nr grid or whose jgpsp is outside 0..255. */
+#define C2D_ROULETTE_GROUPS_MAX 32
+typedef struct {
+  int64_t n_before, n_after, n_tested;   /* n_tested: records with ew < w */
+  double e_before, e_after, kernel_ms;
+} c2d_roulette_out;
+int  c2d_census_stats(c2d_ctx* ctx, const int32_t* group_of_sp, int32_t ngroup,
+                      int64_t* count, double* energy);
+/* device time of the last c2d_census_stats kernel (0 before the first) */
+int  c2d_last_census_stats_ms(c2d_ctx* ctx, double* ms);
+int  c2d_census_roulette(c2d_ctx* ctx, const int32_t* group_of_sp, int32_t ngroup,
+                         const double* w_min, uint64_t salt, c2d_roulette_out* out);
+int  c2d_census_roulette_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
+                              int32_t nz, int32_t nr, const int32_t* group_of_sp, int32_t ngroup,
+                              const double* w_min, uint64_t salt, uint8_t* keep, double* ew_out);
+
 /* The census as the record file of write_cens / read_cens (census2d.f:1-76),
  * formatted on the device: two lines a record, (6e14.7) rpre zpre wmu phi ew
  * xnu and (6i5) jgpsp jgplc jgpmu jph kph seed, 116 bytes with their

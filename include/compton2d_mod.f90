@@ -83,6 +83,14 @@ module compton2d
   ! ---- Fokker-Planck update (c2d_fp_set_config / c2d_fp_step) ----
   integer, parameter :: C2D_FP_NDIAG = 8, C2D_FP_STEPS = 5, C2D_FP_SKIPPED = 6
 
+  ! census population control (c2d_census_stats / c2d_census_roulette)
+  integer, parameter :: C2D_ROULETTE_GROUPS_MAX = 32
+
+  type, bind(C) :: c2d_roulette_out
+     integer(c_int64_t) :: n_before = 0, n_after = 0, n_tested = 0   ! n_tested: records with ew < w
+     real(c_double) :: e_before = 0, e_after = 0, kernel_ms = 0
+  end type c2d_roulette_out
+
   type, bind(C) :: c2d_marray3
      type(c_ptr) :: data = c_null_ptr
      integer(c_int64_t) :: s_i = 0, s_j = 0, s_k = 0
@@ -699,5 +707,53 @@ module compton2d
        integer(c_int64_t), value :: cap
        integer(c_int64_t), intent(out) :: n
      end function c2d_census_export_range
+
+     ! census population control (include/compton2d.h): per (cell, group)
+     ! counts and ew sums, tables (ngroup, nr, nz) in Fortran order
+     integer(c_int) function c2d_census_stats(ctx, group_of_sp, ngroup, count, energy) &
+          bind(C, name='c2d_census_stats')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       integer(c_int64_t), intent(out) :: count(*)
+       real(c_double), intent(out) :: energy(*)
+     end function c2d_census_stats
+
+     integer(c_int) function c2d_last_census_stats_ms(ctx, ms) bind(C, name='c2d_last_census_stats_ms')
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: ms
+     end function c2d_last_census_stats_ms
+
+     ! weight-window roulette of the census against the floors w_min; salt is
+     ! a 64-bit word (the step number)
+     integer(c_int) function c2d_census_roulette(ctx, group_of_sp, ngroup, w_min, salt, res) &
+          bind(C, name='c2d_census_roulette')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t, c2d_roulette_out
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       real(c_double), intent(in) :: w_min(*)
+       integer(c_int64_t), value :: salt
+       type(c2d_roulette_out), intent(out) :: res
+     end function c2d_census_roulette
+
+     ! the same rule on the host: no context, no GPU
+     integer(c_int) function c2d_census_roulette_host(d6, i5, keys, n, nz, nr, group_of_sp, ngroup, &
+          w_min, salt, keep, ew_out) bind(C, name='c2d_census_roulette_host')
+       import :: c_int, c_double, c_int8_t, c_int32_t, c_int64_t
+       real(c_double), intent(in) :: d6(6, *)
+       integer(c_int32_t), intent(in) :: i5(5, *)
+       integer(c_int64_t), intent(in) :: keys(*)
+       integer(c_int64_t), value :: n
+       integer(c_int32_t), value :: nz, nr
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       real(c_double), intent(in) :: w_min(*)
+       integer(c_int64_t), value :: salt
+       integer(c_int8_t), intent(out) :: keep(*)
+       real(c_double), intent(out) :: ew_out(*)
+     end function c2d_census_roulette_host
   end interface
 end module compton2d
