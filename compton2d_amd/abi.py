@@ -686,3 +686,15 @@ class RouletteOut(C.Structure):
     """c2d_roulette_out: what one c2d_census_roulette pass did."""
     _fields_ = [("n_before", _i64), ("n_after", _i64), ("n_tested", _i64),
                 ("e_before", _d), ("e_after", _d), ("kernel_ms", _d)]
+
+
+# ---- the census comb (c2d_census_comb_hist / c2d_census_comb_collect) ----
+COMB_BINS = 2048                    # C2D_COMB_BINS
+COMB_PREFIX_BITS = (0, 11, 22, 33, 44, 55)   # the digits' positions (csrc/c2d_comb.h)
+COMB_STEPS = 8                      # C2D_COMB_STEPS
+
+
+class CombOut(C.Structure):
+    """c2d_comb_out: the counts and the device time of one c2d_census_comb_hist pass."""
+    _fields_ = [("n_records", _i64), ("n_fixed", _i64), ("n_pool", _i64), ("n_match", _i64),
+                ("kernel_ms", _d)]

@@ -55,7 +55,10 @@ class CoupledRun:
         census (summed over ranks through its stats_allreduce) exceeds
         target * (1 + slack), the floors of popcontrol.weight_floor are
         applied with salt = ncycle, and the step's row gains census_before,
-        census_after and roulette_ms.  None (the default) changes nothing."""
+        census_after and roulette_ms; with CensusControl(exact=True) the
+        floors are popcontrol.comb_floor's, which leave exactly `target`
+        records, and the row also gains comb_ms and comb_passes.  None (the
+        default) changes nothing."""
         self.eng, self.wl = eng, wl
         self.census_control = census_control
         self._groups = None

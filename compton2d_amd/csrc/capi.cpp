@@ -21,6 +21,7 @@
 #include "c2d_rng.h"
 #include "reflect_host.h"
 #include "c2d_censfmt.h"
+#include "c2d_comb.hpp"
 #include "c2d_roulette.hpp"
 
 extern "C" int c2d_launch_transport_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
@@ -1857,11 +1858,8 @@ struct RlBufs {
   double* energy;               /* [ncell * ngroup] (stats) */
 };
 
-/* the context's roulette allocation cut for nbins (cell, group) pairs, the group table uploaded */
-static int roulette_bufs(c2d_ctx* c, const int32_t* group_of_sp, int64_t nbins, RlBufs* b) {
-  const size_t head = (sizeof(RouletteCtl) + 255) / 256 * 256, grp = 768,
-               need = head + grp + 3 * sizeof(double) * (size_t)nbins;
-  static_assert(sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "roulette buffer layout");
+/* the context's population-control allocation holds at least `need` bytes */
+static int rl_reserve(c2d_ctx* c, size_t need) {
   if (c->rl_bytes < need) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->rl_buf) (void)hipFree(c->rl_buf);
@@ -1870,6 +1868,15 @@ static int roulette_bufs(c2d_ctx* c, const int32_t* group_of_sp, int64_t nbins, 
     HIPCHK(c, dalloc(&c->rl_buf, need));
     c->rl_bytes = need;
   }
+  return C2D_OK;
+}
+
+/* that allocation cut for nbins (cell, group) pairs, the group table uploaded */
+static int roulette_bufs(c2d_ctx* c, const int32_t* group_of_sp, int64_t nbins, RlBufs* b) {
+  const size_t head = (sizeof(RouletteCtl) + 255) / 256 * 256, grp = 768,
+               need = head + grp + 3 * sizeof(double) * (size_t)nbins;
+  static_assert(sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "roulette buffer layout");
+  { const int rc = rl_reserve(c, need); if (rc) return rc; }
   b->ctl = reinterpret_cast<RouletteCtl*>(c->rl_buf);
   b->group = reinterpret_cast<int32_t*>(c->rl_buf + head);
   b->w_min = reinterpret_cast<double*>(c->rl_buf + head + grp);
@@ -2006,6 +2013,136 @@ extern "C" int c2d_census_roulette_host(const double* d6, const int32_t* i5, con
     const int g = group_of_sp[c2d_roulette_sp((uint32_t)q[0])];
     const double w = w_min[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + g];
     keep[i] = c2d_roulette_decide(d6[6 * i + 4], w, keys[i], salt, ew_out + i) != C2D_ROULETTE_REMOVED ? 1 : 0;
+  }
+  return C2D_OK;
+}
+
+/* ---- the census comb (c2d_comb.h, comb.hip) ---- */
+/* what both device calls and the host twin judge before anything runs (c may be NULL: the host twin) */
+static int comb_args(c2d_ctx* c, const char* who, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
+                     int64_t ncell, uint64_t prefix, int32_t prefix_bits) {
+  { const int rc = roulette_args(c, who, group_of_sp, ngroup); if (rc) return rc; }
+  for (int64_t i = 0; i < ncell * ngroup; i++)
+    if (norm[i] > 0.0 && std::isfinite(norm[i]) && !c2d_comb_pow2(norm[i]))
+      return fail(c, C2D_E_ARG, "%s: norm[%lld] = %.17g is not a power of two", who, (long long)i, norm[i]);
+  if (!c2d_comb_prefix_ok(prefix, (int)prefix_bits))
+    return fail(c, C2D_E_ARG, "%s: prefix %#llx of %d bits (0, 11, 22, 33, 44 or 55 bits, none above them)", who,
+                (unsigned long long)prefix, (int)prefix_bits);
+  return C2D_OK;
+}
+
+struct CombBufs {
+  CombCtl* ctl;
+  int32_t* group;             /* [C2D_ROULETTE_NSP] */
+  unsigned long long* hist;   /* [C2D_COMB_BINS]    */
+  double* norm;               /* [ncell * ngroup]   */
+};
+
+/* one pass of comb.hip over the census: the tables uploaded, counters and histogram zeroed, the
+ * kernel between the context's census events; vals == NULL: the histogram pass */
+static int comb_pass(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* norm, uint64_t salt,
+                     uint64_t prefix, int32_t prefix_bits, double* vals, int64_t cap, CombBufs* b) {
+  const int64_t nbins = (int64_t)c->ncell * ngroup;
+  static_assert(sizeof(CombCtl) <= 256 && sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "comb buffer layout");
+  const size_t hist_at = 256 + 768, norm_at = hist_at + sizeof(unsigned long long) * C2D_COMB_BINS;
+  { const int rc = rl_reserve(c, norm_at + sizeof(double) * (size_t)nbins); if (rc) return rc; }
+  b->ctl = reinterpret_cast<CombCtl*>(c->rl_buf);
+  b->group = reinterpret_cast<int32_t*>(c->rl_buf + 256);
+  b->hist = reinterpret_cast<unsigned long long*>(c->rl_buf + hist_at);
+  b->norm = reinterpret_cast<double*>(c->rl_buf + norm_at);
+  HIPCHK(c, hipMemsetAsync(c->rl_buf, 0, norm_at, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b->group, group_of_sp, sizeof(int32_t) * C2D_ROULETTE_NSP, hipMemcpyHostToDevice,
+                           c->stream));
+  HIPCHK(c, hipMemcpyAsync(b->norm, norm, sizeof(double) * (size_t)nbins, hipMemcpyHostToDevice, c->stream));
+  /* test knob: few workgroups make a small census run the tile loop */
+  int grid_cap = 0;
+  if (const char* e = getenv("C2D_COMB_GRID")) grid_cap = std::max(1, atoi(e));
+  if (!c->cens_ev[0]) HIPCHK(c, hipEventCreate(&c->cens_ev[0]));
+  if (!c->cens_ev[1]) HIPCHK(c, hipEventCreate(&c->cens_ev[1]));
+  HIPCHK(c, hipEventRecord(c->cens_ev[0], c->stream));
+  HIPCHK(c, (hipError_t)c2d_launch_census_comb(c->cens[c->cur].soa(), cens_list(c), c->n_census, c->nz, c->nr,
+                                               (int)ngroup, b->group, b->norm, salt, prefix, (int)prefix_bits,
+                                               vals ? nullptr : b->hist, vals, cap, b->ctl, c->n_cu, grid_cap,
+                                               c->stream));
+  HIPCHK(c, hipEventRecord(c->cens_ev[1], c->stream));
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_comb_hist(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
+                                    uint64_t salt, uint64_t prefix, int32_t prefix_bits, uint64_t* hist,
+                                    c2d_comb_out* out) {
+  if (!c) return C2D_E_ARG;
+  if (!group_of_sp || !norm || !hist || !out) return fail(c, C2D_E_ARG, "c2d_census_comb_hist: a null pointer");
+  { const int rc = comb_args(c, "c2d_census_comb_hist", group_of_sp, ngroup, norm, c->ncell, prefix, prefix_bits);
+    if (rc) return rc; }
+  if (c->census_lost) return census_lost(c, "c2d_census_comb_hist");
+  const c2d_comb_out zero = {};
+  *out = zero;
+  memset(hist, 0, sizeof(uint64_t) * C2D_COMB_BINS);
+  if (c->n_census == 0) return C2D_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  CombBufs b;
+  { const int rc = comb_pass(c, group_of_sp, ngroup, norm, salt, prefix, prefix_bits, nullptr, 0, &b);
+    if (rc) return rc; }
+  CombCtl res = {};
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the histogram is copied as it is");
+  HIPCHK(c, hipMemcpyAsync(hist, b.hist, sizeof(uint64_t) * C2D_COMB_BINS, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&res, b.ctl, sizeof res, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->cens_ev[0], c->cens_ev[1]));
+  out->n_records = c->n_census;
+  out->n_fixed = (int64_t)res.n_fixed;
+  out->n_pool = c->n_census - (int64_t)res.n_fixed;
+  out->n_match = (int64_t)res.n_match;
+  out->kernel_ms = (double)ms;
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_comb_collect(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
+                                       uint64_t salt, uint64_t prefix, int32_t prefix_bits, double* crit_host,
+                                       int64_t cap, int64_t* n) {
+  if (!c) return C2D_E_ARG;
+  if (!group_of_sp || !norm || !n || cap < 0 || (cap > 0 && !crit_host))
+    return fail(c, C2D_E_ARG, "c2d_census_comb_collect: a null pointer or a negative cap");
+  { const int rc = comb_args(c, "c2d_census_comb_collect", group_of_sp, ngroup, norm, c->ncell, prefix, prefix_bits);
+    if (rc) return rc; }
+  if (c->census_lost) return census_lost(c, "c2d_census_comb_collect");
+  *n = 0;
+  if (c->n_census == 0) return C2D_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  /* the values are staged in the packed-record scratch: C2D_CENSUS_REC_WORDS doubles a record of it */
+  const int64_t stage = std::min(cap, c->n_census);
+  { const int rc = ensure_tmp(c, (stage + C2D_CENSUS_REC_WORDS - 1) / C2D_CENSUS_REC_WORDS); if (rc) return rc; }
+  double* vals = reinterpret_cast<double*>(c->tmp_rec);
+  CombBufs b;
+  { const int rc = comb_pass(c, group_of_sp, ngroup, norm, salt, prefix, prefix_bits, vals, stage, &b);
+    if (rc) return rc; }
+  CombCtl res = {};
+  HIPCHK(c, hipMemcpyAsync(&res, b.ctl, sizeof res, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int64_t got = std::min<int64_t>((int64_t)res.n_collect, stage);
+  if (got > 0) HIPCHK(c, hipMemcpy(crit_host, vals, sizeof(double) * (size_t)got, hipMemcpyDeviceToHost));
+  *n = (int64_t)res.n_collect;
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_comb_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n, int32_t nz,
+                                    int32_t nr, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
+                                    uint64_t salt, double* crit, uint8_t* fixed) {
+  if (n < 0 || nz < 1 || nz > C2D_MAXZONE || nr < 1 || nr > C2D_MAXZONE || !group_of_sp || !norm) return C2D_E_ARG;
+  if (n > 0 && (!d6 || !i5 || !keys || !crit || !fixed)) return C2D_E_ARG;
+  if (comb_args(nullptr, "c2d_census_comb_host", group_of_sp, ngroup, norm, (int64_t)nz * nr, 0, 0)) return C2D_E_ARG;
+  for (int64_t i = 0; i < n; i++)
+    if (i5[5 * i] < 0 || i5[5 * i] > 255) return C2D_E_ARG;
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t* q = i5 + 5 * i;
+    const int on_grid = q[3] >= 1 && q[3] <= nz && q[4] >= 1 && q[4] <= nr;
+    double nm = 0.0;
+    if (on_grid) nm = norm[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + group_of_sp[c2d_roulette_sp((uint32_t)q[0])]];
+    const double ew = d6[6 * i + 4];
+    fixed[i] = c2d_comb_fixed(ew, nm, on_grid) ? 1 : 0;
+    crit[i] = fixed[i] ? 0.0 : c2d_comb_critical(ew, nm, keys[i], salt);
   }
   return C2D_OK;
 }

@@ -141,6 +141,15 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_census_roulette_host.restype = C.c_int
     lib.c2d_census_roulette_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.c2d_census_comb_hist.restype = C.c_int
+    lib.c2d_census_comb_hist.argtypes = [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32,
+                                         C.c_void_p, C.POINTER(abi.CombOut)]
+    lib.c2d_census_comb_collect.restype = C.c_int
+    lib.c2d_census_comb_collect.argtypes = [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32,
+                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    lib.c2d_census_comb_host.restype = C.c_int
+    lib.c2d_census_comb_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.c2d_census_import.restype = C.c_int
     lib.c2d_census_import.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_uint64), C.c_int64]
@@ -463,6 +472,36 @@ class Engine:
                                                  w.ctypes.data if w is not None else None,
                                                  int(salt) & 0xFFFFFFFFFFFFFFFF, C.byref(out)))
         return {k: getattr(out, k) for k, _ in abi.RouletteOut._fields_}
+
+    def _comb_tables(self, group_of_sp, ngroup: int, norm):
+        g = self._group_table(group_of_sp)
+        nm = np.ascontiguousarray(norm, np.float64)
+        if nm.size != self.nz * self.nr * int(ngroup) and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX:
+            raise ValueError("norm holds %d entries, %d expected" % (nm.size, self.nz * self.nr * int(ngroup)))
+        return g, nm
+
+    def census_comb_hist(self, group_of_sp, ngroup: int, norm, salt: int, prefix: int = 0, prefix_bits: int = 0):
+        """(hist int64 [2048], out dict): the digit histogram of the pool
+        records' normalised critical values under the prefix
+        (c2d_census_comb_hist; the rule: popcontrol.comb_critical), and
+        n_records, n_fixed, n_pool, n_match, kernel_ms.  The census is unchanged."""
+        g, nm = self._comb_tables(group_of_sp, ngroup, norm)
+        hist, out = np.zeros(abi.COMB_BINS, np.uint64), abi.CombOut()
+        self._check(self.lib.c2d_census_comb_hist(self.ctx, g.ctypes.data, int(ngroup), nm.ctypes.data,
+                                                  int(salt) & 0xFFFFFFFFFFFFFFFF, int(prefix), int(prefix_bits),
+                                                  hist.ctypes.data, C.byref(out)))
+        return hist.astype(np.int64), {k: getattr(out, k) for k, _ in abi.CombOut._fields_}
+
+    def census_comb_collect(self, group_of_sp, ngroup: int, norm, salt: int, prefix: int, prefix_bits: int,
+                            cap: int):
+        """(values f64 [min(n, cap)], n): the normalised critical values under
+        the prefix, in any order, and their full number (c2d_census_comb_collect)."""
+        g, nm = self._comb_tables(group_of_sp, ngroup, norm)
+        vals, n = np.zeros(max(int(cap), 1)), C.c_int64()
+        self._check(self.lib.c2d_census_comb_collect(self.ctx, g.ctypes.data, int(ngroup), nm.ctypes.data,
+                                                     int(salt) & 0xFFFFFFFFFFFFFFFF, int(prefix), int(prefix_bits),
+                                                     vals.ctypes.data, int(cap), C.byref(n)))
+        return vals[:min(n.value, int(cap))], n.value
 
     def import_census(self, d6, i5, keys) -> None:
         d6 = np.ascontiguousarray(d6, np.float64)

@@ -24,6 +24,14 @@ Python-integer `derive_int` / `draw_int` beside it as the plain restatement
 of csrc/c2d_rng.h.  `weight_floor` is the default policy that turns
 Engine.census_stats into floors, `groups_by_decade` the default spectral
 grouping, `CensusControl` what CoupledRun takes.
+
+`weight_floor` only bounds the expected count.  The comb (csrc/c2d_comb.h,
+DESIGN.md 4k) picks floors under which the same roulette pass leaves exactly
+`target` records: `comb_critical` is the yardstick of a record's normalised
+critical floor, `comb_threshold` the search for the (M + 1)-th largest of
+them from digit histograms (Engine.census_comb_hist) and a final collection
+(Engine.census_comb_collect), `comb_floor` the policy, and
+CensusControl(exact=True) what switches CoupledRun to it.
 """
 from __future__ import annotations
 
@@ -220,6 +228,265 @@ def expected_survivors(ew, w) -> float:
     return float((~t).sum() + (ew[t] / w[t]).sum())
 
 
+# ---- the census comb: floors that leave exactly `target` records -------------
+# csrc/c2d_comb.h restated.  Under the roulette a tested record survives the
+# floor w iff S(w) := u < ew / w; its critical floor w* is the largest finite
+# double with S(w*), and it stays iff w <= w*.  With floors t * norm (norm a
+# power of two per (cell, group)) the normalised critical value c = w* / norm
+# is the record's priority (Duffield, Lund & Thorup 2007): the floors keep
+# exactly the records with c >= t, so t one step above the (M+1)-th largest c
+# keeps M of them, and E[ew'] = ew still holds record by record.
+_DBL_MAX_BITS = np.uint64(0x7FEFFFFFFFFFFFFF)
+_TINY = 5e-324
+
+
+def _survives(ew, u, w) -> np.ndarray:
+    with np.errstate(divide="ignore", over="ignore", under="ignore", invalid="ignore"):
+        return u < ew / w
+
+
+def comb_wstar(ew, u) -> np.ndarray:
+    """w* of records of weight ew >= 0 (finite) whose roulette draws are u:
+    start at ew / u (an infinite quotient taken as DBL_MAX), at most
+    abi.COMB_STEPS single steps down while S fails, then up while S holds one
+    step above (c2d_comb_wstar)."""
+    ew = np.ascontiguousarray(ew, np.float64).reshape(-1)
+    u = np.ascontiguousarray(u, np.float64).reshape(-1)
+    with np.errstate(divide="ignore", over="ignore", under="ignore", invalid="ignore"):
+        w = np.minimum((ew / u).view(np.uint64), _DBL_MAX_BITS).view(np.float64)
+    for _ in range(abi.COMB_STEPS):
+        down = (w > 0) & ~_survives(ew, u, w)
+        if not down.any():
+            break
+        w[down] = np.nextafter(w[down], -np.inf)
+    for _ in range(abi.COMB_STEPS):
+        with np.errstate(over="ignore"):                   # the step above DBL_MAX is +inf: S fails there
+            above = np.nextafter(w, np.inf)
+        up = _survives(ew, u, above)
+        if not up.any():
+            break
+        w[up] = above[up]
+    return np.where(ew == 0, 0.0, w)
+
+
+def is_pow2(x) -> np.ndarray:
+    """x positive, finite and a power of two."""
+    x = np.asarray(x, np.float64)
+    with np.errstate(invalid="ignore"):
+        return (x > 0) & np.isfinite(x) & (np.frexp(np.where(np.isfinite(x), x, 0.0))[0] == 0.5)
+
+
+def _comb_tables(group_of_sp, ngroup: int, norm, nz: int, nr: int):
+    g = np.asarray(group_of_sp, np.int64).reshape(-1)
+    if g.size != abi.ROULETTE_NSP or not 1 <= ngroup <= abi.ROULETTE_GROUPS_MAX:
+        raise ValueError("group_of_sp of %d entries, ngroup %d" % (g.size, ngroup))
+    if g.min() < 0 or g.max() >= ngroup:
+        raise ValueError("a group id outside 0..%d" % (ngroup - 1))
+    nm = np.asarray(norm, np.float64).reshape(nz, nr, ngroup)
+    with np.errstate(invalid="ignore"):
+        bad = (nm > 0) & np.isfinite(nm) & ~is_pow2(nm)
+    if bad.any():
+        raise ValueError("a norm that is not a power of two: %r" % float(nm[bad][0]))
+    return g, nm
+
+
+def comb_critical(d6, i5, keys, nz: int, nr: int, group_of_sp, ngroup: int, norm,
+                  salt: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The yardstick of c2d_comb.h on n records in the layout of
+    Engine.census(): (crit f64 [n], fixed bool [n]).  crit is the normalised
+    critical value c = w* / norm of a pool record and 0 for a fixed one: no
+    floor t * norm removes a record with !(norm > 0), norm not finite,
+    !(ew >= 0), ew not finite or a cell off the grid."""
+    d6 = np.asarray(d6, np.float64).reshape(-1, 6)
+    i5 = np.asarray(i5, np.int64).reshape(-1, 5)
+    keys = np.asarray(keys, np.uint64).reshape(-1)
+    g, nm = _comb_tables(group_of_sp, ngroup, norm, nz, nr)
+    if len(i5) and (i5[:, 0].min() < 0 or i5[:, 0].max() > 255):
+        raise ValueError("a record's jgpsp is outside 0..255")
+    ew = d6[:, 4]
+    j, k = i5[:, 3], i5[:, 4]
+    on = (j >= 1) & (j <= nz) & (k >= 1) & (k <= nr)
+    rec_norm = np.where(on, nm[np.clip(j, 1, nz) - 1, np.clip(k, 1, nr) - 1, g[np.minimum(i5[:, 0], abi.NPHOMAX)]],
+                        0.0)
+    with np.errstate(invalid="ignore"):
+        fixed = ~on | ~(rec_norm > 0) | ~np.isfinite(rec_norm) | ~(ew >= 0) | ~np.isfinite(ew)
+    crit = np.zeros(len(ew))
+    p = ~fixed
+    if p.any():
+        with np.errstate(over="ignore", under="ignore"):
+            crit[p] = comb_wstar(ew[p], roulette_u(keys[p], salt)) / rec_norm[p]
+    return crit, fixed
+
+
+def comb_critical_host(d6, i5, keys, nz: int, nr: int, group_of_sp, ngroup: int, norm, salt: int):
+    """The same through the library's host twin (c2d_census_comb_host; no GPU)."""
+    from . import engine
+    lib = engine.load_library()
+    d6 = np.ascontiguousarray(d6, np.float64).reshape(-1, 6)
+    i5 = np.ascontiguousarray(i5, np.int32).reshape(-1, 5)
+    keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+    g = np.ascontiguousarray(group_of_sp, np.int32).reshape(-1)
+    nm = np.ascontiguousarray(norm, np.float64)
+    n = len(keys)
+    if g.size != abi.ROULETTE_NSP or nm.size != int(nz) * int(nr) * int(ngroup):
+        raise ValueError("group_of_sp of %d entries, norm of %d" % (g.size, nm.size))
+    crit, fixed = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.uint8)
+    rc = lib.c2d_census_comb_host(d6.ctypes.data, i5.ctypes.data, keys.ctypes.data, n, int(nz), int(nr),
+                                  g.ctypes.data, int(ngroup), nm.ctypes.data, int(salt) & M64,
+                                  crit.ctypes.data, fixed.ctypes.data)
+    if rc != 0:
+        raise engine.C2DError(rc, "c2d_census_comb_host rejected its arguments")
+    return crit[:n], fixed[:n].astype(bool)
+
+
+def _comb_prefix_check(prefix: int, prefix_bits: int) -> None:
+    if prefix_bits not in abi.COMB_PREFIX_BITS or prefix < 0 or prefix >> prefix_bits:
+        raise ValueError("prefix %#x of %d bits: 0, 11, 22, 33, 44 or 55 bits, none above them" % (prefix, prefix_bits))
+
+
+def comb_match(crit, prefix: int, prefix_bits: int) -> np.ndarray:
+    """The values whose top prefix_bits bits are `prefix`."""
+    _comb_prefix_check(prefix, prefix_bits)
+    b = np.ascontiguousarray(crit, np.float64).view(np.uint64)
+    if prefix_bits == 0:
+        return np.ones(b.shape, bool)
+    return (b >> np.uint64(64 - prefix_bits)) == np.uint64(prefix)
+
+
+def comb_hist_numpy(crit, fixed, prefix: int = 0, prefix_bits: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """What c2d_census_comb_hist returns for records with these (crit, fixed):
+    (hist int64 [2048] of the digit below the prefix, counts int64 [4] =
+    n_records, n_fixed, n_pool, n_match)."""
+    crit = np.ascontiguousarray(crit, np.float64).reshape(-1)
+    fixed = np.asarray(fixed, bool).reshape(-1)
+    pool = crit[~fixed]
+    b = pool[comb_match(pool, prefix, prefix_bits)].view(np.uint64)
+    if prefix_bits == abi.COMB_PREFIX_BITS[-1]:
+        digit = b & np.uint64(0x1FF)
+    else:
+        digit = (b >> np.uint64(64 - 11 - prefix_bits)) & np.uint64(0x7FF)
+    hist = np.bincount(digit.astype(np.int64), minlength=abi.COMB_BINS).astype(np.int64)
+    return hist, np.array([len(crit), int(fixed.sum()), len(pool), len(b)], np.int64)
+
+
+def comb_norm(count, energy, min_per_group: int = 32) -> np.ndarray:
+    """The comb's normalisers: a (cell, group)'s mean weight rounded up to a
+    power of two where it holds at least min_per_group records, 0 (its records
+    are fixed) for the sparse ones: weight_floor's groups and protection."""
+    count = np.asarray(count, np.int64)
+    energy = np.asarray(energy, np.float64)
+    norm = np.zeros(count.shape, np.float64)
+    dense = (count >= max(int(min_per_group), 1)) & (energy > 0) & np.isfinite(energy)
+    raw = energy[dense] / count[dense]
+    ok = np.isfinite(raw) & (raw > 0)
+    nm = np.zeros(raw.shape)
+    nm[ok] = pow2_ceil(raw[ok])
+    norm[dense] = np.where(np.isfinite(nm), nm, 0.0)
+    return norm
+
+
+def comb_threshold(hist_pass: Callable, collect_pass: Optional[Callable], target: int,
+                   collect_cap: int = 1 << 20) -> Tuple[Optional[float], dict]:
+    """The comb's t: one step above the (M + 1)-th largest normalised critical
+    value, M = target - n_fixed, by a most-significant-digit search.
+
+    hist_pass(prefix, prefix_bits) -> (hist, counts, ms), as comb_hist_numpy
+    gives them, summed over ranks; collect_pass(prefix, prefix_bits, bucket)
+    -> the bucket's values of all ranks, or None: then every digit is found
+    by histogram.  The search collects as soon as its bucket holds at most
+    collect_cap values, and finishes with numpy's partition.  Returns
+    (None, info) when the pool is no larger than M (no floor is needed), and
+    raises ValueError for M < 1.  info: passes, collected, comb_ms, n_fixed,
+    n_pool, quota."""
+    if target <= 0:
+        raise ValueError("comb_threshold: target must be positive")
+    info = dict(passes=0, collected=0, comb_ms=0.0, n_fixed=0, n_pool=0, quota=0)
+    prefix, pbits, k = 0, 0, 0
+    while True:
+        hist, counts, ms = hist_pass(prefix, pbits)
+        hist = np.asarray(hist, np.int64)
+        info["passes"] += 1
+        info["comb_ms"] += float(ms)
+        if pbits == 0:
+            n_fixed, n_pool = int(counts[1]), int(counts[2])
+            quota = int(target) - n_fixed
+            info.update(n_fixed=n_fixed, n_pool=n_pool, quota=quota)
+            if quota >= n_pool:
+                return None, info
+            if quota < 1:
+                raise ValueError("comb: target %d is below what the %d protected records alone hold"
+                                 % (target, n_fixed))
+            k = quota + 1                                   # the rank sought, from the top
+        if int(hist.sum()) != int(counts[3]) or k > int(counts[3]):
+            raise RuntimeError("comb: a histogram of %d values, %d matching, rank %d"
+                               % (int(hist.sum()), int(counts[3]), k))
+        above = np.cumsum(hist[::-1])                       # values in the top 1, 2, ... bins
+        i = int(np.searchsorted(above, k, side="left"))
+        d = abi.COMB_BINS - 1 - i
+        k -= int(above[i] - hist[d])
+        bucket = int(hist[d])
+        width = 9 if pbits == abi.COMB_PREFIX_BITS[-1] else 11
+        prefix, pbits = (prefix << width) | d, pbits + width
+        if pbits == 64:
+            cbits = np.uint64(prefix)
+            break
+        if collect_pass is not None and bucket <= collect_cap:
+            vals = np.ascontiguousarray(collect_pass(prefix, pbits, bucket), np.float64)
+            if len(vals) != bucket:
+                raise RuntimeError("comb: %d values collected of a bucket of %d" % (len(vals), bucket))
+            cbits = np.partition(vals.view(np.uint64), bucket - k)[bucket - k]
+            info["collected"] = bucket
+            break
+    return float(np.nextafter(np.array(cbits, np.uint64).view(np.float64), np.inf)), info
+
+
+def comb_weights(t: Optional[float], norm) -> np.ndarray:
+    """The floors t * norm (exact: norm is a power of two), 0 where norm is;
+    all 0 for t = None.  A product that underflows to 0 is taken as the
+    smallest double, which still removes the records of weight 0 and no other."""
+    norm = np.asarray(norm, np.float64)
+    if t is None:
+        return np.zeros(norm.shape)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        live = (norm > 0) & np.isfinite(norm)
+        return np.where(live, np.maximum(t * np.where(live, norm, 1.0), _TINY), 0.0)
+
+
+def comb_floor(eng, groups: Tuple[np.ndarray, int], count, energy, target: int, salt: int,
+               min_per_group: int = 32, collect_cap: int = 1 << 20, hist_allreduce: Optional[Callable] = None,
+               gather: Optional[Callable] = None) -> Tuple[np.ndarray, dict]:
+    """Floors under which Engine.census_roulette(group_of_sp, ngroup, w_min,
+    salt), with the same salt, leaves exactly `target` records (summed over
+    ranks): (w_min [nz, nr, ngroup], info).
+
+    count, energy: Engine.census_stats (summed over ranks); the normalisers
+    are comb_norm's.  hist_allreduce: callable(hist, counts) -> (hist, counts)
+    summed over the ranks after every histogram pass; gather: callable(values)
+    -> the values of all ranks.  With hist_allreduce and no gather all six
+    digits are found by histogram.  `Exactly`: fewer than target only where
+    several records share the (M + 1)-th largest value (duplicated keys)."""
+    g, ng = groups
+    norm = comb_norm(count, energy, min_per_group)
+
+    def hist_pass(prefix, pbits):
+        hist, out = eng.census_comb_hist(g, ng, norm, salt, prefix, pbits)
+        counts = np.array([out["n_records"], out["n_fixed"], out["n_pool"], out["n_match"]], np.int64)
+        if hist_allreduce is not None:
+            hist, counts = hist_allreduce(hist, counts)
+        return hist, counts, out["kernel_ms"]
+
+    def collect_pass(prefix, pbits, bucket):
+        vals, n = eng.census_comb_collect(g, ng, norm, salt, prefix, pbits, bucket)
+        if n > bucket:
+            raise RuntimeError("comb: %d values under a prefix the histogram counted %d for" % (n, bucket))
+        return gather(vals) if gather is not None else vals
+
+    use_collect = hist_allreduce is None or gather is not None
+    t, info = comb_threshold(hist_pass, collect_pass if use_collect else None, target, collect_cap)
+    info["t"] = t
+    return comb_weights(t, norm), info
+
+
 @dataclass
 class CensusControl:
     """What CoupledRun(census_control=...) takes.
@@ -229,20 +496,33 @@ class CensusControl:
     ngroup), default groups_by_decade of the run's spectral grid.
     stats_allreduce: callable(count, energy) -> (count, energy) summed over
     the ranks of a multi-GPU run, so every rank applies the same floors and
-    a record's fate does not depend on the sharding."""
+    a record's fate does not depend on the sharding.  exact: the floors are
+    comb_floor's, which leave exactly `target` records, instead of
+    weight_floor's, which bound the expected count; a multi-GPU run then also
+    gives hist_allreduce and, to shorten the search, gather (comb_floor).  A
+    target below what the protected (sparse-group) records alone hold is a
+    ValueError there."""
     target: int
     slack: float = 0.25
     groups: Optional[Tuple[np.ndarray, int]] = None
     min_per_group: int = 32
     stats_allreduce: Optional[Callable] = None
+    exact: bool = False
+    hist_allreduce: Optional[Callable] = None
+    gather: Optional[Callable] = None
 
 
 def apply_control(eng, ctl: CensusControl, groups: Tuple[np.ndarray, int], salt: int) -> dict:
     """One population-control decision on `eng`'s census: census_before,
     census_after (this context's records) and roulette_ms (0 when the pass
-    did not run)."""
+    did not run); with ctl.exact also comb_ms and comb_passes, the device
+    time and the histogram passes of comb_floor."""
     before = eng.census_count()
     row = dict(census_before=before, census_after=before, roulette_ms=0.0)
+    if ctl.exact:
+        row.update(comb_ms=0.0, comb_passes=0)
+        if ctl.stats_allreduce is not None and ctl.hist_allreduce is None:
+            raise ValueError("CensusControl(exact=True) over several ranks needs hist_allreduce")
     limit = ctl.target * (1.0 + ctl.slack)
     if ctl.stats_allreduce is None and before <= limit:
         return row
@@ -252,6 +532,12 @@ def apply_control(eng, ctl: CensusControl, groups: Tuple[np.ndarray, int], salt:
         count, energy = ctl.stats_allreduce(count, energy)
     if int(np.sum(count)) <= limit:
         return row
-    out = eng.census_roulette(g, ng, weight_floor(count, energy, ctl.target, ctl.min_per_group), salt)
+    if ctl.exact:
+        w_min, info = comb_floor(eng, groups, count, energy, ctl.target, salt, ctl.min_per_group,
+                                 hist_allreduce=ctl.hist_allreduce, gather=ctl.gather)
+        row.update(comb_ms=info["comb_ms"], comb_passes=info["passes"])
+    else:
+        w_min = weight_floor(count, energy, ctl.target, ctl.min_per_group)
+    out = eng.census_roulette(g, ng, w_min, salt)
     row.update(census_after=out["n_after"], roulette_ms=out["kernel_ms"])
     return row

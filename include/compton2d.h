@@ -550,6 +550,57 @@ int  c2d_census_roulette_host(const double* d6, const int32_t* i5, const uint64_
                               int32_t nz, int32_t nr, const int32_t* group_of_sp, int32_t ngroup,
                               const double* w_min, uint64_t salt, uint8_t* keep, double* ew_out);
 
+/* Census comb: floors that leave exactly a wanted number of records
+ * (csrc/c2d_comb.h, csrc/comb.hip).  Opt-in, as the roulette.
+ *
+ * Under c2d_census_roulette a record of weight ew whose draw is u survives
+ * the floor w iff u < ew / w; its critical floor w* is the largest finite
+ * double for which that holds (0 for ew = 0), and it stays iff w <= w*.
+ * With floors t * norm[jph-1][kph-1][g], norm a power of two, a record's
+ * normalised critical value is c = w* / norm, and the floors keep exactly
+ * the records with c >= t: t one step above the (M+1)-th largest c keeps M
+ * of them.  These calls find that value where the census lies; the floors
+ * are then applied by c2d_census_roulette with the same group_of_sp and the
+ * same salt.  A record is `fixed`, kept by every floor of the family, if
+ * !(norm > 0), norm is not finite, !(ew >= 0), ew is not finite or its cell
+ * is off the grid; the others are the pool.
+ *
+ * The 64-bit pattern of c >= 0 orders as an unsigned integer and is read in
+ * six digits: bits 63-53, 52-42, 41-31, 30-20, 19-9 (11 bits each) and 8-0.
+ * prefix_bits is 0, 11, 22, 33, 44 or 55, and `prefix` holds that many bits.
+ *
+ * c2d_census_comb_hist: hist[d] = the pool records whose c has `prefix` in
+ * its top prefix_bits bits and d as its next digit, exactly; out->n_pool the
+ * pool, n_match the histogram's sum, n_fixed, n_records, kernel_ms the device
+ * time of the pass.
+ *
+ * c2d_census_comb_collect: the c of those records to crit_host, in any order
+ * and at most cap of them; *n is their full number, so *n <= cap says that
+ * all arrived.
+ *
+ * Both leave the census exactly as it is.  Errors: C2D_E_ARG, before
+ * anything runs, as for c2d_census_roulette and for a norm entry that is
+ * positive and finite but no power of two, a prefix_bits off the list or a
+ * prefix with bits above prefix_bits; C2D_E_STATE if the census was lost.
+ *
+ * c2d_census_comb_host: c and the fixed flag (crit 0 there) of n records in
+ * the layout of c2d_census_export, norm [nz][nr][ngroup].  Needs no context
+ * and no GPU; C2D_E_ARG also for a jgpsp outside 0..255. */
+#define C2D_COMB_BINS 2048
+typedef struct {
+  int64_t n_records, n_fixed, n_pool, n_match;
+  double kernel_ms;
+} c2d_comb_out;
+int  c2d_census_comb_hist(c2d_ctx* ctx, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
+                          uint64_t salt, uint64_t prefix, int32_t prefix_bits, uint64_t hist[C2D_COMB_BINS],
+                          c2d_comb_out* out);
+int  c2d_census_comb_collect(c2d_ctx* ctx, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
+                             uint64_t salt, uint64_t prefix, int32_t prefix_bits, double* crit_host, int64_t cap,
+                             int64_t* n);
+int  c2d_census_comb_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
+                          int32_t nz, int32_t nr, const int32_t* group_of_sp, int32_t ngroup,
+                          const double* norm, uint64_t salt, double* crit, uint8_t* fixed);
+
 /* The census as the record file of write_cens / read_cens (census2d.f:1-76),
  * formatted on the device: two lines a record, (6e14.7) rpre zpre wmu phi ew
  * xnu and (6i5) jgpsp jgplc jgpmu jph kph seed, 116 bytes with their

@@ -91,6 +91,14 @@ module compton2d
      real(c_double) :: e_before = 0, e_after = 0, kernel_ms = 0
   end type c2d_roulette_out
 
+  ! the census comb (c2d_census_comb_hist / c2d_census_comb_collect)
+  integer, parameter :: C2D_COMB_BINS = 2048
+
+  type, bind(C) :: c2d_comb_out
+     integer(c_int64_t) :: n_records = 0, n_fixed = 0, n_pool = 0, n_match = 0
+     real(c_double) :: kernel_ms = 0
+  end type c2d_comb_out
+
   type, bind(C) :: c2d_marray3
      type(c_ptr) :: data = c_null_ptr
      integer(c_int64_t) :: s_i = 0, s_j = 0, s_k = 0
@@ -755,5 +763,53 @@ module compton2d
        integer(c_int8_t), intent(out) :: keep(*)
        real(c_double), intent(out) :: ew_out(*)
      end function c2d_census_roulette_host
+
+     ! the census comb (include/compton2d.h): the digit histogram of the pool
+     ! records' normalised critical values under `prefix` (prefix_bits = 0,
+     ! 11, 22, 33, 44 or 55); norm (ngroup, nr, nz) in Fortran order, powers of two
+     integer(c_int) function c2d_census_comb_hist(ctx, group_of_sp, ngroup, norm, salt, prefix, &
+          prefix_bits, hist, res) bind(C, name='c2d_census_comb_hist')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t, c2d_comb_out
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       real(c_double), intent(in) :: norm(*)
+       integer(c_int64_t), value :: salt, prefix
+       integer(c_int32_t), value :: prefix_bits
+       integer(c_int64_t), intent(out) :: hist(0:*)
+       type(c2d_comb_out), intent(out) :: res
+     end function c2d_census_comb_hist
+
+     ! those records' values to crit_host (at most cap); n = their full number
+     integer(c_int) function c2d_census_comb_collect(ctx, group_of_sp, ngroup, norm, salt, prefix, &
+          prefix_bits, crit_host, cap, n) bind(C, name='c2d_census_comb_collect')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       real(c_double), intent(in) :: norm(*)
+       integer(c_int64_t), value :: salt, prefix
+       integer(c_int32_t), value :: prefix_bits
+       real(c_double), intent(out) :: crit_host(*)
+       integer(c_int64_t), value :: cap
+       integer(c_int64_t), intent(out) :: n
+     end function c2d_census_comb_collect
+
+     ! the same values on the host: no context, no GPU
+     integer(c_int) function c2d_census_comb_host(d6, i5, keys, n, nz, nr, group_of_sp, ngroup, &
+          norm, salt, crit, fixed) bind(C, name='c2d_census_comb_host')
+       import :: c_int, c_double, c_int8_t, c_int32_t, c_int64_t
+       real(c_double), intent(in) :: d6(6, *)
+       integer(c_int32_t), intent(in) :: i5(5, *)
+       integer(c_int64_t), intent(in) :: keys(*)
+       integer(c_int64_t), value :: n
+       integer(c_int32_t), value :: nz, nr
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       real(c_double), intent(in) :: norm(*)
+       integer(c_int64_t), value :: salt
+       real(c_double), intent(out) :: crit(*)
+       integer(c_int8_t), intent(out) :: fixed(*)
+     end function c2d_census_comb_host
   end interface
 end module compton2d

@@ -26,8 +26,9 @@ printed beside it.  Roofline: 8.0 TB/s (the HBM3E peak; a float4 copy reaches
 6.3 TB/s).
 
 --c3: the C3 workload at reduced size (--sources volume packets a step,
---steps steps, FP on), 16 seeds with and without a CensusControl at
-target = 1/4 of the uncontrolled run's last census: mean step time of the
+--steps steps, FP on), 16 seeds without a CensusControl, with one at
+target = 1/4 of the uncontrolled run's last census, and with the same one
+made exact (the comb's floors, popcontrol.comb_floor): mean step time of the
 last half of the steps, the census there, and the relative scatter over the
 seeds (standard deviation / mean, per bin) of the SED summed over those steps
 (the fout tally), as its energy-weighted mean over the bins.
@@ -131,10 +132,11 @@ def c3(sources, steps, seeds):
     target = int(np.mean([f[2] for f in free]) / 4)
     ctl = PC.CensusControl(target=target)
     held = [c3_run(sources, steps, 1000 + s, ctl) for s in range(seeds)]
+    combed = [c3_run(sources, steps, 1000 + s, PC.CensusControl(target=target, exact=True)) for s in range(seeds)]
     leg = lambda rs: {"step_ms": float(np.mean([r[1] for r in rs])), "census": float(np.mean([r[2] for r in rs])),
                       "roulette_kernel_ms": float(np.mean([r[3] for r in rs])), "sed_rel_scatter": scatter([r[0] for r in rs])}
     return {"sources": sources, "steps": steps, "seeds": seeds, "target": target, "slack": ctl.slack,
-            "uncontrolled": leg(free), "controlled": leg(held),
+            "uncontrolled": leg(free), "controlled": leg(held), "controlled_exact": leg(combed),
             "note": "means over the last half of the steps; step_ms is host time around CoupledRun.step"}
 
 
