@@ -688,6 +688,18 @@ class RouletteOut(C.Structure):
                 ("e_before", _d), ("e_after", _d), ("kernel_ms", _d)]
 
 
+# ---- census splitting (c2d_census_split) ----
+SPLIT_COPIES_MAX = 64               # C2D_SPLIT_COPIES_MAX
+SPLIT_DRY = 1                       # C2D_SPLIT_DRY: count only
+TAG_SPLIT = 0x0D                    # C2D_TAG_SPLIT (csrc/c2d_rng.h)
+
+
+class SplitOut(C.Structure):
+    """c2d_split_out: what one c2d_census_split pass did (or, dry, would do)."""
+    _fields_ = [("n_before", _i64), ("n_after", _i64), ("n_split", _i64),
+                ("e_before", _d), ("e_after", _d), ("kernel_ms", _d)]
+
+
 # ---- the census comb (c2d_census_comb_hist / c2d_census_comb_collect) ----
 COMB_BINS = 2048                    # C2D_COMB_BINS
 COMB_PREFIX_BITS = (0, 11, 22, 33, 44, 55)   # the digits' positions (csrc/c2d_comb.h)

@@ -57,8 +57,11 @@ class CoupledRun:
         applied with salt = ncycle, and the step's row gains census_before,
         census_after and roulette_ms; with CensusControl(exact=True) the
         floors are popcontrol.comb_floor's, which leave exactly `target`
-        records, and the row also gains comb_ms and comb_passes.  None (the
-        default) changes nothing."""
+        records, and the row also gains comb_ms and comb_passes; with
+        CensusControl(ceiling_ratio=...) records far heavier than their
+        (cell, group)'s mean are split afterwards, the census permitting
+        (popcontrol.apply_control), and the row also gains split_copies,
+        split_ms and split_skipped.  None (the default) changes nothing."""
         self.eng, self.wl = eng, wl
         self.census_control = census_control
         self._groups = None

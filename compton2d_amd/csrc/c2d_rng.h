@@ -39,6 +39,9 @@
  *   roulette key     = derive(K_census, TAG_ROULETTE, salt lo, salt hi): its draw 0
  *                      decides a census record's survival (c2d_roulette.h); the
  *                      record's own streams, drawn from K_census directly, are untouched
+ *   split copy i     = derive(K_census, TAG_SPLIT, salt lo, salt hi; sub i), i = 1..m-1:
+ *                      the census key of copy i of a record split m-fold by the upper
+ *                      weight window (c2d_split.h); copy 0 keeps K_census
  *   compb2d's first rejection loop (compb_2d.f:59-93): iteration j draws
  *                      counters c0 + 5j .. c0 + 5j + 4 of the packet's stream (c0:
  *                      the counter at the call), the rest of compb2d follows
@@ -69,6 +72,7 @@
 #define C2D_TAG_SCAT3   0x0Au
 #define C2D_TAG_CENSUS  0x0Bu
 #define C2D_TAG_ROULETTE 0x0Cu  /* census population control (c2d_roulette.h) */
+#define C2D_TAG_SPLIT   0x0Du   /* census splitting (c2d_split.h) */
 
 #define C2D_DRAW_C3     0x5EEDD1CEu
 #define C2D_DERIVE_C3   0x9E3779B9u

@@ -23,6 +23,7 @@
 #include "c2d_censfmt.h"
 #include "c2d_comb.hpp"
 #include "c2d_roulette.hpp"
+#include "c2d_split.hpp"
 
 extern "C" int c2d_launch_transport_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
                                           int trk, int refl, hipStream_t s);
@@ -1786,12 +1787,39 @@ extern "C" int c2d_census_pack(c2d_ctx* c, int64_t first, int64_t n, uint64_t* d
   return C2D_OK;
 }
 
+/* the census holds n more records than it does: C2D_E_CENSUS_OVERFLOW with
+ * nothing written otherwise */
+static int census_fits(c2d_ctx* c, const char* who, int64_t n) {
+  if (c->n_census + n > c->cfg.census_capacity)
+    return fail(c, C2D_E_CENSUS_OVERFLOW, "%s: %lld + %lld > capacity %lld", who, (long long)c->n_census,
+                (long long)n, (long long)c->cfg.census_capacity);
+  return C2D_OK;
+}
+
+/* room for n more records behind the census (chunked): the list's last chunk
+ * fills up first, then free chunks join the list.  A failure leaves the
+ * census as it was. */
+static int census_chunks_extend(c2d_ctx* c, const char* who, int64_t n) {
+  if (!c->chunked) return C2D_OK;
+  const int64_t k = (c->n_census + n + C2D_CCHUNK - 1) / C2D_CCHUNK - c->n_clist;
+  if (k > 0) {
+    int64_t n_free = 0;
+    int rc = chunk_pool_build(c, &n_free);
+    if (rc) return rc;
+    if (n_free < k)
+      return fail(c, C2D_E_CENSUS_OVERFLOW, "%s: %lld free census chunks, %lld needed", who, (long long)n_free,
+                  (long long)k);
+    HIPCHK(c, hipMemcpyAsync(c->clist[c->ccur] + c->n_clist, c->pool, sizeof(int32_t) * k,
+                             hipMemcpyDeviceToDevice, c->stream));
+    c->n_clist += k;
+  }
+  return C2D_OK;
+}
+
 extern "C" int c2d_census_append(c2d_ctx* c, const uint64_t* d_rec, int64_t n) {
   if (!c || n < 0 || (n > 0 && !d_rec)) return C2D_E_ARG;
   if (c->census_lost) return census_lost(c, "c2d_census_append");
-  if (c->n_census + n > c->cfg.census_capacity)
-    return fail(c, C2D_E_CENSUS_OVERFLOW, "c2d_census_append: %lld + %lld > capacity %lld",
-                (long long)c->n_census, (long long)n, (long long)c->cfg.census_capacity);
+  { const int rc = census_fits(c, "c2d_census_append", n); if (rc) return rc; }
   if (n == 0) return C2D_OK;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   {   /* every record carries its cell and E_ph bin (c2d_cens_jk) */
@@ -1806,21 +1834,7 @@ extern "C" int c2d_census_append(c2d_ctx* c, const uint64_t* d_rec, int64_t n) {
     if (bad) return fail(c, C2D_E_ARG, "c2d_census_append: a record without its cell or E_ph bin (c2d_census_pack "
                          "format, include/compton2d.h)");
   }
-  if (c->chunked) {
-    /* the list's last chunk fills up first, then free chunks join the list */
-    const int64_t k = (c->n_census + n + C2D_CCHUNK - 1) / C2D_CCHUNK - c->n_clist;
-    if (k > 0) {
-      int64_t n_free = 0;
-      int rc = chunk_pool_build(c, &n_free);
-      if (rc) return rc;
-      if (n_free < k)
-        return fail(c, C2D_E_CENSUS_OVERFLOW, "c2d_census_append: %lld free census chunks, %lld needed",
-                    (long long)n_free, (long long)k);
-      HIPCHK(c, hipMemcpyAsync(c->clist[c->ccur] + c->n_clist, c->pool, sizeof(int32_t) * k,
-                               hipMemcpyDeviceToDevice, c->stream));
-      c->n_clist += k;
-    }
-  }
+  { const int rc = census_chunks_extend(c, "c2d_census_append", n); if (rc) return rc; }
   const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)c->n_cu * 8);
   hipLaunchKernelGGL(c2d_census_unpack_kernel, dim3(grid), dim3(256), 0, c->stream,
                      c->cens[c->cur].soa(), cens_list(c), c->n_census, n, d_rec);
@@ -2014,6 +2028,145 @@ extern "C" int c2d_census_roulette_host(const double* d6, const int32_t* i5, con
     const double w = w_min[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + g];
     keep[i] = c2d_roulette_decide(d6[6 * i + 4], w, keys[i], salt, ew_out + i) != C2D_ROULETTE_REMOVED ? 1 : 0;
   }
+  return C2D_OK;
+}
+
+/* ---- census splitting (c2d_split.h, split.hip) ---- */
+static int split_args(c2d_ctx* c, const char* who, const int32_t* group_of_sp, int32_t ngroup, int32_t max_copies) {
+  { const int rc = roulette_args(c, who, group_of_sp, ngroup); if (rc) return rc; }
+  if (max_copies < 2 || max_copies > C2D_SPLIT_COPIES_MAX)
+    return fail(c, C2D_E_ARG, "%s: max_copies %d outside 2..%d", who, (int)max_copies, C2D_SPLIT_COPIES_MAX);
+  return C2D_OK;
+}
+
+struct SpBufs {
+  SplitCtl* ctl;
+  int32_t* group;     /* [C2D_ROULETTE_NSP] */
+  double* w_max;      /* [ncell * ngroup]   */
+  int64_t* off;       /* [ntiles]           */
+  uint32_t* cnt;      /* [ntiles]           */
+};
+
+/* the pass itself; *began = the census has been (or may have been) rewritten */
+static int split_body(c2d_ctx* c, const SpBufs& b, int32_t ngroup, int32_t max_copies, uint64_t salt, bool dry,
+                      hipEvent_t e0, hipEvent_t e1, hipEvent_t e2, SplitCtl* res, float* ms, bool* began) {
+  const int64_t n = c->n_census, ntiles = sp_tiles(n);
+  const CensusSoA cs = c->cens[c->cur].soa();
+  int64_t strip = SP_SCAN_STRIP;
+  /* test knob: short strips give the scan several rounds on a small census */
+  if (const char* e = getenv("C2D_SPLIT_STRIP")) strip = std::max<int64_t>(1, std::min<int64_t>(strip, atoll(e)));
+  HIPCHK(c, hipMemsetAsync(b.ctl, 0, sizeof(SplitCtl), c->stream));
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  HIPCHK(c, (hipError_t)c2d_launch_split_count(cs, cens_list(c), n, c->nz, c->nr, (int)ngroup, b.group, b.w_max,
+                                               (int)max_copies, b.cnt, b.ctl, c->n_cu, c->stream));
+  HIPCHK(c, (hipError_t)c2d_launch_split_scan(b.cnt, ntiles, strip, b.off, b.ctl, c->stream));
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res, b.ctl, sizeof *res, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   /* the only wait: the room to make depends on the total */
+  HIPCHK(c, hipEventElapsedTime(ms, e0, e1));
+  const int64_t extra = (int64_t)res->n_extra;
+  if (extra < (int64_t)res->n_split || extra > (int64_t)res->n_split * (C2D_SPLIT_COPIES_MAX - 1))
+    return fail(c, C2D_E_STATE, "c2d_census_split: %lld copies of %llu split records", (long long)extra, res->n_split);
+  if (dry || extra == 0) return C2D_OK;
+  { const int rc = census_fits(c, "c2d_census_split", extra); if (rc) return rc; }
+  { const int rc = census_chunks_extend(c, "c2d_census_split", extra); if (rc) return rc; }
+  *began = true;
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, (hipError_t)c2d_launch_split_expand(cs, cens_list(c), n, n + extra, c->nz, c->nr, (int)ngroup, b.group,
+                                                b.w_max, (int)max_copies, salt, b.cnt, b.off, c->n_cu, c->stream));
+  HIPCHK(c, hipEventRecord(e2, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms2 = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms2, e1, e2));
+  *ms += ms2;
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_split(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* w_max,
+                                int32_t max_copies, uint64_t salt, int32_t flags, c2d_split_out* out) {
+  if (!c) return C2D_E_ARG;
+  if (!group_of_sp || !w_max || !out) return fail(c, C2D_E_ARG, "c2d_census_split: a null pointer");
+  { const int rc = split_args(c, "c2d_census_split", group_of_sp, ngroup, max_copies); if (rc) return rc; }
+  if (flags & ~C2D_SPLIT_DRY) return fail(c, C2D_E_ARG, "c2d_census_split: unknown flag bits %#x", (unsigned)flags);
+  if (c->census_lost) return census_lost(c, "c2d_census_split");
+  const c2d_split_out zero = {};
+  *out = zero;
+  out->n_before = out->n_after = c->n_census;
+  if (c->n_census == 0) return C2D_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int64_t nbins = (int64_t)c->ncell * ngroup, ntiles = sp_tiles(c->n_census);
+  SpBufs b;
+  {
+    const size_t head = 256, grp = 768, tab = (sizeof(double) * (size_t)nbins + 255) / 256 * 256,
+                 offs = (sizeof(int64_t) * (size_t)ntiles + 255) / 256 * 256;
+    static_assert(sizeof(SplitCtl) <= 256 && sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "split buffer layout");
+    { const int rc = rl_reserve(c, head + grp + tab + offs + sizeof(uint32_t) * (size_t)ntiles); if (rc) return rc; }
+    b.ctl = reinterpret_cast<SplitCtl*>(c->rl_buf);
+    b.group = reinterpret_cast<int32_t*>(c->rl_buf + head);
+    b.w_max = reinterpret_cast<double*>(c->rl_buf + head + grp);
+    b.off = reinterpret_cast<int64_t*>(c->rl_buf + head + grp + tab);
+    b.cnt = reinterpret_cast<uint32_t*>(c->rl_buf + head + grp + tab + offs);
+  }
+  HIPCHK(c, hipMemcpyAsync(b.group, group_of_sp, sizeof(int32_t) * C2D_ROULETTE_NSP, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b.w_max, w_max, sizeof(double) * (size_t)nbins, hipMemcpyHostToDevice, c->stream));
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; i++)
+    if (hipEventCreate(&ev[i]) != hipSuccess) {
+      for (int k = 0; k < i; k++) (void)hipEventDestroy(ev[k]);
+      return fail(c, C2D_E_HIP, "c2d_census_split: hipEventCreate");
+    }
+  SplitCtl res = {};
+  float ms = 0.f;
+  bool began = false;
+  const int rc = split_body(c, b, ngroup, max_copies, salt, (flags & C2D_SPLIT_DRY) != 0, ev[0], ev[1], ev[2], &res,
+                            &ms, &began);
+  for (int i = 0; i < 3; i++) (void)hipEventDestroy(ev[i]);
+  if (rc) {
+    if (began) {   /* partly rewritten: lost, as after a failed in-place step */
+      (void)hipStreamSynchronize(c->stream);
+      c->n_census = 0;
+      if (c->chunked) c->n_clist = 0;
+      c->census_lost = true;
+    }
+    return rc;
+  }
+  out->n_after = c->n_census + (int64_t)res.n_extra;
+  out->n_split = (int64_t)res.n_split;
+  out->e_before = res.e_before;
+  out->e_after = res.e_after;
+  out->kernel_ms = (double)ms;
+  if (!(flags & C2D_SPLIT_DRY)) c->n_census = out->n_after;
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_split_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n, int32_t nz,
+                                     int32_t nr, const int32_t* group_of_sp, int32_t ngroup, const double* w_max,
+                                     int32_t max_copies, uint64_t salt, int32_t* copies, double* ew_out) {
+  (void)salt;   /* the weights and the counts do not depend on it: the copies' keys do (c2d_split_key) */
+  if (n < 0 || nz < 1 || nz > C2D_MAXZONE || nr < 1 || nr > C2D_MAXZONE || !group_of_sp || !w_max) return C2D_E_ARG;
+  if (n > 0 && (!d6 || !i5 || !keys || !copies || !ew_out)) return C2D_E_ARG;
+  if (split_args(nullptr, "c2d_census_split_host", group_of_sp, ngroup, max_copies)) return C2D_E_ARG;
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t* q = i5 + 5 * i;
+    if (q[3] < 1 || q[3] > nz || q[4] < 1 || q[4] > nr || q[0] < 0 || q[0] > 255) return C2D_E_ARG;
+  }
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t* q = i5 + 5 * i;
+    const int g = group_of_sp[c2d_roulette_sp((uint32_t)q[0])];
+    const double W = w_max[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + g];
+    copies[i] = c2d_split_copies(d6[6 * i + 4], W, (int)max_copies, ew_out + i);
+  }
+  return C2D_OK;
+}
+
+extern "C" int c2d_census_split_keys_host(const uint64_t* keys, const int32_t* copies, int64_t n, uint64_t salt,
+                                          uint64_t* keys_out) {
+  if (n < 0 || (n > 0 && (!keys || !copies || !keys_out))) return C2D_E_ARG;
+  for (int64_t i = 0; i < n; i++)
+    if (copies[i] < 1 || copies[i] > C2D_SPLIT_COPIES_MAX) return C2D_E_ARG;
+  int64_t o = 0;
+  for (int64_t i = 0; i < n; i++)
+    for (int k = 1; k < copies[i]; k++) keys_out[o++] = c2d_split_key(keys[i], salt, k);
   return C2D_OK;
 }
 

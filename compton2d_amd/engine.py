@@ -141,6 +141,15 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_census_roulette_host.restype = C.c_int
     lib.c2d_census_roulette_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.c2d_census_split.restype = C.c_int
+    lib.c2d_census_split.argtypes = [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32,
+                                     C.POINTER(abi.SplitOut)]
+    lib.c2d_census_split_host.restype = C.c_int
+    lib.c2d_census_split_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p,
+                                          C.c_void_p]
+    lib.c2d_census_split_keys_host.restype = C.c_int
+    lib.c2d_census_split_keys_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]
     lib.c2d_census_comb_hist.restype = C.c_int
     lib.c2d_census_comb_hist.argtypes = [vp, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32,
                                          C.c_void_p, C.POINTER(abi.CombOut)]
@@ -472,6 +481,26 @@ class Engine:
                                                  w.ctypes.data if w is not None else None,
                                                  int(salt) & 0xFFFFFFFFFFFFFFFF, C.byref(out)))
         return {k: getattr(out, k) for k, _ in abi.RouletteOut._fields_}
+
+    def census_split(self, group_of_sp, ngroup: int, w_max, max_copies: int, salt: int,
+                     dry_run: bool = False) -> dict:
+        """Split the census records heavier than the ceilings w_max [nz, nr,
+        ngroup] into at most max_copies records each (c2d_census_split; the
+        rule: popcontrol.split_numpy).  dry_run: only count, the census stays
+        as it is.  Returns n_before, n_after, n_split, e_before, e_after,
+        kernel_ms."""
+        g = self._group_table(group_of_sp)
+        w = None
+        if w_max is not None:
+            w = np.ascontiguousarray(w_max, np.float64)
+            if w.size != self.nz * self.nr * int(ngroup) and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX:
+                raise ValueError("w_max holds %d ceilings, %d expected" % (w.size, self.nz * self.nr * int(ngroup)))
+        out = abi.SplitOut()
+        self._check(self.lib.c2d_census_split(self.ctx, g.ctypes.data, int(ngroup),
+                                              w.ctypes.data if w is not None else None, int(max_copies),
+                                              int(salt) & 0xFFFFFFFFFFFFFFFF, abi.SPLIT_DRY if dry_run else 0,
+                                              C.byref(out)))
+        return {k: getattr(out, k) for k, _ in abi.SplitOut._fields_}
 
     def _comb_tables(self, group_of_sp, ngroup: int, norm):
         g = self._group_table(group_of_sp)

@@ -43,6 +43,7 @@ import numpy as np
 from . import abi
 
 M64 = 0xFFFFFFFFFFFFFFFF
+_TINY = 5e-324
 M32 = 0xFFFFFFFF
 _PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 _PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
@@ -85,26 +86,40 @@ def _u64(x) -> np.ndarray:
     return np.asarray(x, np.uint64)
 
 
-def roulette_u(keys, salt: int) -> np.ndarray:
-    """roulette_u_int of every key, vectorised (uint64 products of 32-bit
-    words are exact; 64-bit products wrap as the C code's do)."""
+def derive_keys(keys, tag: int, a: int, b: int, sub=0) -> np.ndarray:
+    """derive_int of every key, vectorised: c2d_derive_s(key, tag, a, b, sub),
+    sub a scalar or one value a key (uint64 products of 32-bit words are
+    exact)."""
     keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
     m32, s32 = np.uint64(M32), np.uint64(32)
-    salt = int(salt) & M64
-    c0 = np.full(keys.shape, salt & M32, np.uint64)
-    c1 = np.full(keys.shape, salt >> 32, np.uint64)
-    c2 = np.full(keys.shape, abi.TAG_ROULETTE, np.uint64)
+    sub = np.broadcast_to(np.asarray(sub, np.uint64), keys.shape)
+    c0 = np.full(keys.shape, int(a) & M32, np.uint64)
+    c1 = np.full(keys.shape, int(b) & M32, np.uint64)
+    c2 = (np.uint64(tag) | (sub << np.uint64(8))) & m32
     c3 = np.full(keys.shape, _DERIVE_C3, np.uint64)
     k0, k1 = keys & m32, keys >> s32
     for _ in range(10):
         p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2
         c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
         k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & m32, (k1 + np.uint64(_PHILOX_W1)) & m32
-    z = ((c1 << s32) | c0) + np.uint64(_GAMMA)            # stream (K, sub 0), draw 0
+    return (c1 << s32) | c0
+
+
+def draw_keys(keys, n: int = 0, sub: int = 0) -> np.ndarray:
+    """draw_int(key, n, sub) of every key, vectorised (64-bit products wrap as
+    the C code's do)."""
+    keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+    z = keys + np.uint64((_GAMMA * (((int(sub) << 32) | int(n)) + 1)) & M64)
     z = (z ^ (z >> np.uint64(30))) * np.uint64(_MIX1)
     z = (z ^ (z >> np.uint64(27))) * np.uint64(_MIX2)
     z = z ^ (z >> np.uint64(31))
     return ((z >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+
+
+def roulette_u(keys, salt: int) -> np.ndarray:
+    """roulette_u_int of every key, vectorised."""
+    salt = int(salt) & M64
+    return draw_keys(derive_keys(keys, abi.TAG_ROULETTE, salt & M32, salt >> 32), 0)
 
 
 def record_floors(i5, nz: int, nr: int, group_of_sp, ngroup: int, w_min) -> np.ndarray:
@@ -228,6 +243,122 @@ def expected_survivors(ew, w) -> float:
     return float((~t).sum() + (ew[t] / w[t]).sum())
 
 
+# ---- census splitting: the upper weight window (csrc/c2d_split.h) -------------
+# A record heavier than its ceiling W = w_max[jph-1, kph-1, g] becomes
+# m = min(max_copies, ceil(ew / W)) records of weight ew / m: copy 0 is the
+# record itself, copy i = 1..m-1 equals it but for its key,
+# derive(key, TAG_SPLIT, salt lo, salt hi; sub i).  Untouched (m = 1):
+# !(W > 0), W or ew not finite, !(ew > W).
+def split_copies(ew, W, max_copies: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(m int32 [n], ew' f64 [n]) of records of weight ew under the ceilings W."""
+    if not 2 <= int(max_copies) <= abi.SPLIT_COPIES_MAX:
+        raise ValueError("max_copies %d outside 2..%d" % (max_copies, abi.SPLIT_COPIES_MAX))
+    ew = np.ascontiguousarray(ew, np.float64).reshape(-1)
+    W = np.ascontiguousarray(W, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        t = (W > 0) & np.isfinite(W) & np.isfinite(ew) & (ew > W)
+        q = ew[t] / W[t]                                   # one IEEE division
+        mt = np.where(~(q < max_copies), float(max_copies), np.ceil(np.where(np.isfinite(q), q, 0.0)))
+    m = np.ones(len(ew), np.int32)
+    m[t] = mt.astype(np.int32)
+    out = ew.copy()
+    out[t] = ew[t] / m[t].astype(np.float64)               # one IEEE division
+    return m, out
+
+
+def split_keys(keys, copies, salt: int) -> np.ndarray:
+    """The keys of the copies i = 1..copies[k]-1 of every record k, ordered by (k, i)."""
+    keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+    extra = np.asarray(copies, np.int64).reshape(-1) - 1
+    src = np.repeat(np.arange(len(keys)), extra)
+    i = np.arange(len(src)) - np.repeat(np.cumsum(extra) - extra, extra) + 1
+    salt = int(salt) & M64
+    return derive_keys(keys[src], abi.TAG_SPLIT, salt & M32, salt >> 32, i.astype(np.uint64))
+
+
+def split_numpy(d6, i5, keys, nz: int, nr: int, group_of_sp, ngroup: int, w_max, max_copies: int, salt: int):
+    """The yardstick of c2d_census_split on n records in the layout of
+    Engine.census(): (copies int32 [n], ew_out f64 [n], (d6, i5, keys)), the
+    last the whole census afterwards in the order the pass guarantees: the n
+    records in place with their new ew, the copies behind them ordered by
+    (source record, i)."""
+    d6 = np.asarray(d6, np.float64).reshape(-1, 6)
+    i5 = np.asarray(i5).reshape(-1, 5)
+    keys = np.asarray(keys, np.uint64).reshape(-1)
+    W = record_floors(i5, nz, nr, group_of_sp, ngroup, w_max)
+    m, ew_out = split_copies(d6[:, 4], W, max_copies)
+    src = np.repeat(np.arange(len(keys)), m.astype(np.int64) - 1)
+    d6o = np.concatenate([d6, d6[src]])
+    d6o[:len(keys), 4] = ew_out
+    d6o[len(keys):, 4] = ew_out[src]
+    return m, ew_out, (d6o, np.concatenate([i5, i5[src]]), np.concatenate([keys, split_keys(keys, m, salt)]))
+
+
+def split_host(d6, i5, keys, nz: int, nr: int, group_of_sp, ngroup: int, w_max, max_copies: int, salt: int):
+    """(copies, ew_out, copy keys) through the library's host twins
+    (c2d_census_split_host, c2d_census_split_keys_host; no GPU)."""
+    from . import engine
+    lib = engine.load_library()
+    d6 = np.ascontiguousarray(d6, np.float64).reshape(-1, 6)
+    i5 = np.ascontiguousarray(i5, np.int32).reshape(-1, 5)
+    keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+    g = np.ascontiguousarray(group_of_sp, np.int32).reshape(-1)
+    w = np.ascontiguousarray(w_max, np.float64)
+    n = len(keys)
+    if g.size != abi.ROULETTE_NSP or (w.size != int(nz) * int(nr) * int(ngroup)
+                                      and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX):
+        raise ValueError("group_of_sp of %d entries, w_max of %d" % (g.size, w.size))
+    m, out = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1))
+    rc = lib.c2d_census_split_host(d6.ctypes.data, i5.ctypes.data, keys.ctypes.data, n, int(nz), int(nr),
+                                   g.ctypes.data, int(ngroup), w.ctypes.data, int(max_copies), int(salt) & M64,
+                                   m.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise engine.C2DError(rc, "c2d_census_split_host rejected its arguments")
+    m, out = m[:n], out[:n]
+    ck = np.zeros(max(int((m.astype(np.int64) - 1).sum()), 1), np.uint64)
+    rc = lib.c2d_census_split_keys_host(keys.ctypes.data, m.ctypes.data, n, int(salt) & M64, ck.ctypes.data)
+    if rc != 0:
+        raise engine.C2DError(rc, "c2d_census_split_keys_host rejected its arguments")
+    return m, out, ck[:int((m.astype(np.int64) - 1).sum())]
+
+
+def weight_ceiling(count, energy, ratio: float, min_per_group: int = 32) -> np.ndarray:
+    """The default ceilings from the census statistics (summed over ranks):
+    `ratio` times a (cell, group)'s mean weight, rounded up to a power of two
+    (so last-bit noise of the f64 sums changes no decision), where the group
+    holds at least min_per_group records; 0, no ceiling, for the sparse
+    groups, whose mean says little."""
+    if not ratio > 1:
+        raise ValueError("weight_ceiling: ratio must exceed 1")
+    count = np.asarray(count, np.int64)
+    energy = np.asarray(energy, np.float64)
+    w = np.zeros(count.shape, np.float64)
+    dense = (count >= max(int(min_per_group), 1)) & (energy > 0) & np.isfinite(energy)
+    with np.errstate(over="ignore"):
+        raw = float(ratio) * energy[dense] / count[dense]
+    ok = np.isfinite(raw) & (raw > 0)
+    cl = np.zeros(raw.shape)
+    cl[ok] = pow2_ceil(raw[ok])
+    w[dense] = np.where(np.isfinite(cl), cl, 0.0)
+    return w
+
+
+def multiply_tables(nz: int, nr: int) -> Tuple[np.ndarray, int, np.ndarray]:
+    """(group_of_sp, ngroup, w_max) under which every record of positive finite
+    weight is split max_copies-fold: one group, the smallest double as every
+    ceiling (a subnormal weight of j steps of 5e-324, j < max_copies, becomes
+    j records: it cannot be divided further)."""
+    return np.zeros(abi.ROULETTE_NSP, np.int32), 1, np.full((nz, nr, 1), _TINY)
+
+
+def multiply(eng, k: int, salt: int) -> dict:
+    """k-fold multiplication of `eng`'s census: every record of positive finite
+    weight becomes k records of weight ew / k on independent streams
+    (Engine.census_split's dict)."""
+    g, ng, w = multiply_tables(eng.nz, eng.nr)
+    return eng.census_split(g, ng, w, int(k), salt)
+
+
 # ---- the census comb: floors that leave exactly `target` records -------------
 # csrc/c2d_comb.h restated.  Under the roulette a tested record survives the
 # floor w iff S(w) := u < ew / w; its critical floor w* is the largest finite
@@ -237,7 +368,6 @@ def expected_survivors(ew, w) -> float:
 # exactly the records with c >= t, so t one step above the (M+1)-th largest c
 # keeps M of them, and E[ew'] = ew still holds record by record.
 _DBL_MAX_BITS = np.uint64(0x7FEFFFFFFFFFFFFF)
-_TINY = 5e-324
 
 
 def _survives(ew, u, w) -> np.ndarray:
@@ -501,7 +631,14 @@ class CensusControl:
     weight_floor's, which bound the expected count; a multi-GPU run then also
     gives hist_allreduce and, to shorten the search, gather (comb_floor).  A
     target below what the protected (sparse-group) records alone hold is a
-    ValueError there."""
+    ValueError there.
+
+    ceiling_ratio: with a value (> 1) the upper window acts as well: after the
+    roulette decision, records heavier than ceiling_ratio times their (cell,
+    group)'s mean weight (weight_ceiling) are split into at most max_copies
+    records, provided the census (summed over ranks) stays within
+    target * (1 + slack); a split that would not is skipped.  None: no
+    splitting, and nothing about the rows changes."""
     target: int
     slack: float = 0.25
     groups: Optional[Tuple[np.ndarray, int]] = None
@@ -510,28 +647,23 @@ class CensusControl:
     exact: bool = False
     hist_allreduce: Optional[Callable] = None
     gather: Optional[Callable] = None
+    ceiling_ratio: Optional[float] = None
+    max_copies: int = 8
 
 
-def apply_control(eng, ctl: CensusControl, groups: Tuple[np.ndarray, int], salt: int) -> dict:
-    """One population-control decision on `eng`'s census: census_before,
-    census_after (this context's records) and roulette_ms (0 when the pass
-    did not run); with ctl.exact also comb_ms and comb_passes, the device
-    time and the histogram passes of comb_floor."""
-    before = eng.census_count()
-    row = dict(census_before=before, census_after=before, roulette_ms=0.0)
-    if ctl.exact:
-        row.update(comb_ms=0.0, comb_passes=0)
-        if ctl.stats_allreduce is not None and ctl.hist_allreduce is None:
-            raise ValueError("CensusControl(exact=True) over several ranks needs hist_allreduce")
+def _roulette_control(eng, ctl: CensusControl, groups, salt: int, row: dict):
+    """The lower window's decision; returns the (summed) statistics of the
+    census as it now is, or None where they were not taken or no longer hold."""
+    before = row["census_before"]
     limit = ctl.target * (1.0 + ctl.slack)
     if ctl.stats_allreduce is None and before <= limit:
-        return row
+        return None
     g, ng = groups
     count, energy = eng.census_stats(g, ng)
     if ctl.stats_allreduce is not None:
         count, energy = ctl.stats_allreduce(count, energy)
     if int(np.sum(count)) <= limit:
-        return row
+        return count, energy
     if ctl.exact:
         w_min, info = comb_floor(eng, groups, count, energy, ctl.target, salt, ctl.min_per_group,
                                  hist_allreduce=ctl.hist_allreduce, gather=ctl.gather)
@@ -540,4 +672,51 @@ def apply_control(eng, ctl: CensusControl, groups: Tuple[np.ndarray, int], salt:
         w_min = weight_floor(count, energy, ctl.target, ctl.min_per_group)
     out = eng.census_roulette(g, ng, w_min, salt)
     row.update(census_after=out["n_after"], roulette_ms=out["kernel_ms"])
+    return None
+
+
+def _split_control(eng, ctl: CensusControl, groups, salt: int, row: dict, stats) -> None:
+    """The upper window's decision: ceilings from the statistics, a dry run,
+    and the split itself only if the census (summed over ranks) stays within
+    target * (1 + slack)."""
+    g, ng = groups
+    if stats is None:
+        stats = eng.census_stats(g, ng)
+        if ctl.stats_allreduce is not None:
+            stats = ctl.stats_allreduce(*stats)
+    w_max = weight_ceiling(stats[0], stats[1], ctl.ceiling_ratio, ctl.min_per_group)
+    dry = eng.census_split(g, ng, w_max, ctl.max_copies, salt, dry_run=True)
+    row.update(split_copies=0, split_ms=dry["kernel_ms"], split_skipped=False)
+    total, extra = dry["n_after"], dry["n_after"] - dry["n_before"]
+    if ctl.stats_allreduce is not None:
+        summed, _ = ctl.stats_allreduce(np.array([total, extra], np.int64), np.zeros(2))
+        total, extra = int(summed[0]), int(summed[1])
+    if extra == 0:
+        return
+    if total > ctl.target * (1.0 + ctl.slack):
+        row["split_skipped"] = True
+        return
+    if dry["n_after"] > dry["n_before"]:
+        out = eng.census_split(g, ng, w_max, ctl.max_copies, salt)
+        row.update(census_after=out["n_after"], split_copies=out["n_after"] - out["n_before"],
+                   split_ms=dry["kernel_ms"] + out["kernel_ms"])
+
+
+def apply_control(eng, ctl: CensusControl, groups: Tuple[np.ndarray, int], salt: int) -> dict:
+    """One population-control decision on `eng`'s census: census_before,
+    census_after (this context's records) and roulette_ms (0 when the pass
+    did not run); with ctl.exact also comb_ms and comb_passes, the device
+    time and the histogram passes of comb_floor; with ctl.ceiling_ratio also
+    split_copies (the records the split added here), split_ms (its device
+    time, the dry run included) and split_skipped (the split would have left
+    more than target * (1 + slack) records and was not made)."""
+    before = eng.census_count()
+    row = dict(census_before=before, census_after=before, roulette_ms=0.0)
+    if ctl.exact:
+        row.update(comb_ms=0.0, comb_passes=0)
+        if ctl.stats_allreduce is not None and ctl.hist_allreduce is None:
+            raise ValueError("CensusControl(exact=True) over several ranks needs hist_allreduce")
+    stats = _roulette_control(eng, ctl, groups, salt, row)
+    if ctl.ceiling_ratio is not None:
+        _split_control(eng, ctl, groups, salt, row, stats)
     return row

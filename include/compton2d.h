@@ -550,6 +550,59 @@ int  c2d_census_roulette_host(const double* d6, const int32_t* i5, const uint64_
                               int32_t nz, int32_t nr, const int32_t* group_of_sp, int32_t ngroup,
                               const double* w_min, uint64_t salt, uint8_t* keep, double* ew_out);
 
+/* Census splitting: the upper weight window, and k-fold multiplication
+ * (csrc/c2d_split.h, csrc/split.hip).  Opt-in, as the roulette;
+ * group_of_sp, ngroup and the table layout are the roulette's.
+ *
+ * c2d_census_split: a record in cell (jph, kph) and group g with
+ * W = w_max[jph-1][kph-1][g] is untouched if !(W > 0), if W or ew is not
+ * finite or if !(ew > W).  Otherwise it becomes m records,
+ * m = min(max_copies, ceil(ew / W)) >= 2 (ew / W one IEEE division), each of
+ * weight ew / m (one IEEE division): copy 0 is the record itself with only
+ * its ew changed, copy i = 1..m-1 equals it word for word but for its key,
+ * which is derived from the record's key with the tag C2D_TAG_SPLIT, `salt`
+ * and the sub i (c2d_rng.h), so the copies fly on independent streams and the
+ * expected value of every tally is unchanged.  2 <= max_copies <=
+ * C2D_SPLIT_COPIES_MAX; use a new salt for every pass (the step number).
+ * The originals keep their places as census items [0, n_before); the copies
+ * are the items [n_before, n_after) in (source item, i) order, so the result
+ * is a function of the census, the ceilings, max_copies and the salt alone,
+ * the same in both census modes and both builds.  With flags =
+ * C2D_SPLIT_DRY the pass only counts: out is what a committed pass would
+ * report, the census stays as it is.  With no ceiling that can test a record
+ * the census is byte for byte what it was.  out: the counts, n_split the
+ * records with m > 1, the sums of ew before and after, kernel_ms the device
+ * time of the pass.
+ *
+ * Errors: C2D_E_ARG, before anything runs, for a null pointer, ngroup, a
+ * group id or max_copies out of range or unknown flag bits; C2D_E_STATE if
+ * the census was lost; C2D_E_CENSUS_OVERFLOW, before a single byte is
+ * written and with the census exactly as it was, if n_after exceeds the
+ * capacity or the free chunks.  A HIP failure after writing has begun leaves
+ * the census lost, as for c2d_census_roulette.
+ *
+ * c2d_census_split_host: the same rule on n records in the layout of
+ * c2d_census_export; copies[i] = m and ew_out[i] = the weight of each of the
+ * m records (ew as given for m = 1).  Needs no context and no GPU; C2D_E_ARG
+ * also for a record whose cell is off the nz x nr grid or whose jgpsp is
+ * outside 0..255.  c2d_census_split_keys_host: the keys of the copies
+ * i = 1..copies[k]-1 of the records k = 0..n-1, in that order
+ * (sum (copies[k] - 1) of them). */
+#define C2D_SPLIT_COPIES_MAX 64
+#define C2D_SPLIT_DRY 1            /* flags: count only, the census stays as it is */
+typedef struct {
+  int64_t n_before, n_after, n_split;   /* n_split: records with m > 1 */
+  double e_before, e_after, kernel_ms;
+} c2d_split_out;
+int  c2d_census_split(c2d_ctx* ctx, const int32_t* group_of_sp, int32_t ngroup, const double* w_max,
+                      int32_t max_copies, uint64_t salt, int32_t flags, c2d_split_out* out);
+int  c2d_census_split_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
+                           int32_t nz, int32_t nr, const int32_t* group_of_sp, int32_t ngroup,
+                           const double* w_max, int32_t max_copies, uint64_t salt,
+                           int32_t* copies /* m per record */, double* ew_out /* ew' per record */);
+int  c2d_census_split_keys_host(const uint64_t* keys, const int32_t* copies, int64_t n, uint64_t salt,
+                                uint64_t* keys_out);
+
 /* Census comb: floors that leave exactly a wanted number of records
  * (csrc/c2d_comb.h, csrc/comb.hip).  Opt-in, as the roulette.
  *

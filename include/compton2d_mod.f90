@@ -91,6 +91,15 @@ module compton2d
      real(c_double) :: e_before = 0, e_after = 0, kernel_ms = 0
   end type c2d_roulette_out
 
+  ! census splitting (c2d_census_split): the upper weight window
+  integer, parameter :: C2D_SPLIT_COPIES_MAX = 64
+  integer(c_int32_t), parameter :: C2D_SPLIT_DRY = 1   ! flags: count only, the census stays as it is
+
+  type, bind(C) :: c2d_split_out
+     integer(c_int64_t) :: n_before = 0, n_after = 0, n_split = 0   ! n_split: records with m > 1
+     real(c_double) :: e_before = 0, e_after = 0, kernel_ms = 0
+  end type c2d_split_out
+
   ! the census comb (c2d_census_comb_hist / c2d_census_comb_collect)
   integer, parameter :: C2D_COMB_BINS = 2048
 
@@ -763,6 +772,51 @@ module compton2d
        integer(c_int8_t), intent(out) :: keep(*)
        real(c_double), intent(out) :: ew_out(*)
      end function c2d_census_roulette_host
+
+     ! census splitting against the ceilings w_max (ngroup, nr, nz) in Fortran
+     ! order: a record heavier than its ceiling becomes up to max_copies
+     ! records; flags = C2D_SPLIT_DRY only counts
+     integer(c_int) function c2d_census_split(ctx, group_of_sp, ngroup, w_max, max_copies, salt, flags, res) &
+          bind(C, name='c2d_census_split')
+       import :: c_int, c_ptr, c_double, c_int32_t, c_int64_t, c2d_split_out
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       real(c_double), intent(in) :: w_max(*)
+       integer(c_int32_t), value :: max_copies
+       integer(c_int64_t), value :: salt
+       integer(c_int32_t), value :: flags
+       type(c2d_split_out), intent(out) :: res
+     end function c2d_census_split
+
+     ! the same rule on the host: no context, no GPU
+     integer(c_int) function c2d_census_split_host(d6, i5, keys, n, nz, nr, group_of_sp, ngroup, &
+          w_max, max_copies, salt, copies, ew_out) bind(C, name='c2d_census_split_host')
+       import :: c_int, c_double, c_int32_t, c_int64_t
+       real(c_double), intent(in) :: d6(6, *)
+       integer(c_int32_t), intent(in) :: i5(5, *)
+       integer(c_int64_t), intent(in) :: keys(*)
+       integer(c_int64_t), value :: n
+       integer(c_int32_t), value :: nz, nr
+       integer(c_int32_t), intent(in) :: group_of_sp(0:*)
+       integer(c_int32_t), value :: ngroup
+       real(c_double), intent(in) :: w_max(*)
+       integer(c_int32_t), value :: max_copies
+       integer(c_int64_t), value :: salt
+       integer(c_int32_t), intent(out) :: copies(*)
+       real(c_double), intent(out) :: ew_out(*)
+     end function c2d_census_split_host
+
+     ! the keys of the copies 1..copies(k)-1 of every record, in that order
+     integer(c_int) function c2d_census_split_keys_host(keys, copies, n, salt, keys_out) &
+          bind(C, name='c2d_census_split_keys_host')
+       import :: c_int, c_int32_t, c_int64_t
+       integer(c_int64_t), intent(in) :: keys(*)
+       integer(c_int32_t), intent(in) :: copies(*)
+       integer(c_int64_t), value :: n
+       integer(c_int64_t), value :: salt
+       integer(c_int64_t), intent(out) :: keys_out(*)
+     end function c2d_census_split_keys_host
 
      ! the census comb (include/compton2d.h): the digit histogram of the pool
      ! records' normalised critical values under `prefix` (prefix_bits = 0,

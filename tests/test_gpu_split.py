@@ -1,0 +1,523 @@
+"""Census splitting on the GPU (c2d_census_split; csrc/split.hip) against the
+numpy yardstick (compton2d_amd/popcontrol.py split_numpy): the pass in both
+census modes and both builds in item order, the shapes that can break its
+kernels, the dry run, overflow, the refusals, that the census still runs
+afterwards, sharding, the interplay with the roulette, unbiasedness in
+transport, and CoupledRun with a ceiling.
+
+The records are real ones: the census a 3x3 C2 workload leaves (the pool of
+test_gpu_roulette.py), so a transport step can carry them on, with their ew
+replaced by a spread of six decades around the ceilings (split_case.spread_ew).
+Tolerances: counts, keys, ew and the order are exact.  e_before and e_after
+are sums of n terms of one sign (e_after: one term m ew' a record) added by
+f64 atomics in any order, each addition rounding by at most 2^-53 of the
+total: n 2^-53 relative at worst.  That is 5.7e-13 for the pool's 5137
+records, so the bound is 1e-12 there; the one larger case (70 001 records)
+takes its own n 2^-53 = 7.8e-12 (sum_tol).
+"""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import pytest
+
+import split_case as SC
+from compton2d_amd import abi, popcontrol as PC, synth
+from compton2d_amd.coupled import CoupledRun
+from compton2d_amd.engine import C2DError, Engine
+from golden_io import GoldenCase
+
+pytestmark = pytest.mark.gpu
+
+NZ = NR = 3
+CAP = 1 << 16
+SIZES = (0, 1, 63, 64, 65, 1023, 1024, 1025, 5 * 1024 + 17)
+NG = 32
+MC = 8
+MODES = [(0, abi.COMTOT_EXACT), (1, abi.COMTOT_EXACT), (0, abi.COMTOT_TABLE), (1, abi.COMTOT_TABLE)]
+TALLY_KEYS = ("edep", "prdep", "ecens", "npcen", "n_field", "E_IC", "nelectron", "fout", "edout",
+              "erlki", "erlko", "erlku", "erlkl", "Ed_in")
+
+
+def workload(mode=abi.COMTOT_EXACT, sources=9, capacity=CAP):
+    return synth.c2_workload(nz=NZ, nr=NR, sources=sources, comtot_mode=mode, census_capacity=capacity,
+                             event_capacity=1 << 16)
+
+
+def grid_of(inplace, mode, capacity=CAP):
+    return dataclasses.replace(workload(mode, capacity=capacity).grid, census_inplace=inplace,
+                               queue_capacity=1 << 16)
+
+
+@pytest.fixture(scope="module")
+def pool():
+    """(d6, i5, keys, g, w): 5137 census records of a 3x3 C2 run, the ones with the
+    smallest keys in key order (so the pool does not depend on the order the
+    device happened to write its census in), their ew spread around the
+    ceilings w [3, 3, 32]; left unchanged by every test."""
+    wl = workload(sources=6000, capacity=1 << 16)
+    with Engine(dataclasses.replace(wl.grid, queue_capacity=1 << 18)) as eng:
+        for n in range(4):
+            nc, t = wl.clock(n)
+            eng.transport_step(dataclasses.replace(wl.step0, ncycle=nc, time=t))
+            if eng.census_count() >= SIZES[-1]:
+                break
+        d6, i5, keys = eng.census()
+    assert len(keys) >= SIZES[-1] and len(np.unique(keys)) == len(keys)
+    o = np.argsort(keys)[:SIZES[-1]]
+    d6, i5, keys = d6[o].copy(), i5[o].copy(), keys[o].copy()
+    g = SC.group_table(NG)
+    w = SC.ceilings(NZ, NR, NG)
+    d6[:, 4] = SC.spread_ew(i5, NZ, NR, w, g)
+    for a in (d6, i5, keys, g, w):
+        a.setflags(write=False)
+    return d6, i5, keys, g, w
+
+
+@pytest.fixture(scope="module", params=MODES, ids=lambda p: "inplace%d-%s" % (p[0], "fast" if p[1] else "exact"))
+def eng(request):
+    inplace, mode = request.param
+    with Engine(grid_of(inplace, mode)) as e:
+        yield e
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint8).reshape(len(a), a.nbytes // max(len(a), 1))
+
+
+def same_census(got, want):
+    """Two censuses equal word for word, order included."""
+    assert len(got[2]) == len(want[2])
+    for a, b in zip(got, want):
+        np.testing.assert_array_equal(bits(a), bits(b))
+
+
+def by_key(d6, i5, keys):
+    o = np.argsort(keys, kind="stable")
+    return d6[o], i5[o], keys[o]
+
+
+def sum_tol(n):
+    return max(1e-12, n * 2.0 ** -53)
+
+
+def check_pass(e, d6, i5, keys, g, ng, w, mc, salt, call=None):
+    """Import the records, run the pass, compare with the yardstick in item order; returns the out dict."""
+    n = len(keys)
+    e.import_census(d6, i5, keys)
+    pre = e.census()
+    out = call(e) if call else e.census_split(g, ng, w, mc, salt)
+    m, ew_new, want = PC.split_numpy(pre[0], pre[1], pre[2], NZ, NR, g, ng, w, mc, salt)
+    n_after = n + int((m.astype(np.int64) - 1).sum())
+    assert (out["n_before"], out["n_after"], out["n_split"]) == (n, n_after, int((m > 1).sum()))
+    assert e.census_count() == n_after
+    e_b, e_a = float(pre[0][:, 4].sum()), float(want[0][:, 4].sum())
+    print("n=%d: %d split, %d after; e_before rel %.2e, e_after rel %.2e" % (
+        n, out["n_split"], n_after, abs(out["e_before"] - e_b) / max(e_b, 1e-300),
+        abs(out["e_after"] - e_a) / max(e_a, 1e-300)))
+    assert out["e_before"] == pytest.approx(e_b, rel=sum_tol(n), abs=0.0)
+    assert out["e_after"] == pytest.approx(e_a, rel=sum_tol(n), abs=0.0)
+    if n_after:
+        post = e.census()
+        # the originals in place: the yardstick's ew bit for bit, every other word as it was
+        np.testing.assert_array_equal(post[0][:n, 4].view(np.uint64), ew_new.view(np.uint64))
+        same_census(post, want)                                  # and the copies behind them, by (source, i)
+    return out
+
+
+# --------------------------------------------------- 1. against the yardstick
+def test_split_equals_yardstick(eng, pool, monkeypatch):
+    d6, i5, keys, g, w = pool
+    for n in SIZES:
+        out = check_pass(eng, d6[:n], i5[:n], keys[:n], g, NG, w, MC, salt=n + 1)
+        if n >= 63:
+            assert 0 < out["n_split"] < n and out["n_after"] > n
+    check_pass(eng, d6, i5, keys, g, NG, w, 2, salt=2 ** 63)
+    check_pass(eng, d6[:1025], i5[:1025], keys[:1025], g, NG, w, 64, salt=2 ** 64 - 1)
+    # the tile scan in strips of 2 tiles: three strips and a carry for the six tiles of the pool
+    monkeypatch.setenv("C2D_SPLIT_STRIP", "2")
+    for n in (1, 1025, 2049, SIZES[-1]):
+        check_pass(eng, d6[:n], i5[:n], keys[:n], g, NG, w, MC, salt=7)
+    monkeypatch.setenv("C2D_SPLIT_STRIP", "1")
+    check_pass(eng, d6[:3000], i5[:3000], keys[:3000], g, NG, w, MC, salt=7)
+
+
+# --------------------------------------- 2. shapes that can break the kernels
+def multiplied(k, salt):
+    return lambda e: PC.multiply(e, k, salt)
+
+
+def test_shapes(eng, pool):
+    d6, i5, keys, _, _ = pool
+    chunked = eng.grid.census_inplace == 1
+    g1, ng1, w1 = PC.multiply_tables(NZ, NR)
+    # a tile with no split record between two that have them (ew = 0 is never split)
+    gap = d6[:3072].copy()
+    gap[1024:2048, 4] = 0.0
+    out = check_pass(eng, gap, i5[:3072], keys[:3072], g1, ng1, w1, 3, 5, multiplied(3, 5))
+    assert out["n_split"] == int((gap[:, 4] > 0).sum()) < 2048
+    # a tile with more than 1024 extras: several trips of the output loop
+    out = check_pass(eng, d6[64:164], i5[64:164], keys[64:164], g1, ng1, w1, 64, 6, multiplied(64, 6))
+    assert out["n_after"] == 100 + 63 * out["n_split"] and out["n_split"] >= 98
+    # one record alone with m = 64
+    out = check_pass(eng, d6[:1], i5[:1], keys[:1], g1, ng1, w1, 64, 7, multiplied(64, 7))
+    assert (out["n_split"], out["n_after"]) == (1, 64)
+    # 1000 records whose copies cross the 1024 and the 2048 item boundaries (chunked: two new chunks)
+    out = check_pass(eng, d6[:1000], i5[:1000], keys[:1000], g1, ng1, w1, 3, 8, multiplied(3, 8))
+    assert out["n_after"] > 2048
+    if chunked:
+        assert eng.last_census_chunks()[0] == -(-out["n_after"] // 1024)
+
+
+@pytest.mark.parametrize("inplace", [0, 1])
+def test_69_tiles_doubled(pool, inplace):
+    """70 001 records are 69 tiles: more tiles than a small grid's workgroups take one each."""
+    d6, i5, keys, _, _ = pool
+    reps = 14
+    big = (np.tile(d6, (reps, 1))[:70001], np.tile(i5, (reps, 1))[:70001],
+           np.concatenate([keys ^ np.uint64(0x9E3779B97F4A7C15 * k & 0xFFFFFFFFFFFFFFFF) for k in range(reps)])[:70001])
+    assert len(np.unique(big[2])) == 70001
+    g1, ng1, w1 = PC.multiply_tables(NZ, NR)
+    with Engine(grid_of(inplace, abi.COMTOT_EXACT, capacity=1 << 18)) as e:
+        out = check_pass(e, *big, g1, ng1, w1, 2, 3, multiplied(2, 3))
+        assert out["n_after"] == 70001 + out["n_split"] and out["n_split"] > 68000
+        if inplace:
+            assert e.last_census_chunks()[0] == -(-out["n_after"] // 1024)
+
+
+# ------------------------------------------------------------------ 3. dry run
+def test_dry_run(eng, pool):
+    d6, i5, keys, g, w = pool
+    eng.import_census(d6, i5, keys)
+    pre = eng.census()
+    dry = eng.census_split(g, NG, w, MC, 4, dry_run=True)
+    assert eng.census_count() == len(keys)
+    same_census(eng.census(), pre)
+    out = eng.census_split(g, NG, w, MC, 4)
+    for k in ("n_before", "n_after", "n_split"):
+        assert dry[k] == out[k]
+    assert dry["e_before"] == pytest.approx(out["e_before"], rel=1e-12)
+    assert dry["e_after"] == pytest.approx(out["e_after"], rel=1e-12)
+    assert out["n_after"] > out["n_before"] == len(keys) and eng.census_count() == out["n_after"]
+    same_census(eng.census(), PC.split_numpy(*pre, NZ, NR, g, NG, w, MC, 4)[2])
+
+
+# ----------------------------------------------------------------- 4. overflow
+@pytest.mark.parametrize("inplace", [0, 1])
+def test_overflow_leaves_the_census_as_it_was(pool, inplace):
+    d6, i5, keys, _, _ = pool
+    with Engine(grid_of(inplace, abi.COMTOT_EXACT, capacity=2048)) as e:
+        e.import_census(d6[:1000], i5[:1000], keys[:1000])
+        pre = e.census()
+        with pytest.raises(C2DError) as err:
+            PC.multiply(e, 3, 1)                                   # 3000 > 2048
+        assert err.value.code == abi.C2D_E_CENSUS_OVERFLOW
+        assert e.census_count() == 1000
+        same_census(e.census(), pre)
+        out = PC.multiply(e, 2, 1)                                 # 2000 fit
+        assert out["n_after"] == 1000 + out["n_split"] <= 2048
+        g1, ng1, w1 = PC.multiply_tables(NZ, NR)
+        same_census(e.census(), PC.split_numpy(*pre, NZ, NR, g1, ng1, w1, 2, 1)[2])
+
+
+# ------------------------------------------- 5. ceilings that test nothing
+def test_ceilings_that_test_nothing(eng, pool):
+    d6, i5, keys, g, _ = pool
+    n = len(keys)
+    for w0 in (np.zeros((NZ, NR, NG)), np.full((NZ, NR, NG), np.nan), np.full((NZ, NR, NG), -np.inf),
+               np.full((NZ, NR, NG), np.inf), np.full((NZ, NR, NG), 1e300)):
+        eng.import_census(d6, i5, keys)
+        pre = eng.census()
+        out = eng.census_split(g, NG, w0, MC, 3)
+        assert (out["n_before"], out["n_after"], out["n_split"]) == (n, n, 0)
+        assert out["e_before"] == pytest.approx(d6[:, 4].sum(), rel=1e-12)
+        assert out["e_after"] == pytest.approx(out["e_before"], rel=1e-12)    # two sums, each in its own order
+        same_census(eng.census(), pre)
+
+
+# ---------------------------------------------------------------- 6. refusals
+def test_refusals_leave_the_census_unchanged(eng, pool):
+    d6, i5, keys, g, w = pool
+    eng.import_census(d6[:500], i5[:500], keys[:500])
+    pre = eng.census()
+    lib, out = eng.lib, abi.SplitOut()
+
+    def call(gt=g, ng=NG, wt=w, mc=MC, flags=0, o=out):
+        gp = gt.ctypes.data if gt is not None else None
+        wp = wt.ctypes.data if wt is not None else None
+        return lib.c2d_census_split(eng.ctx, gp, ng, wp, mc, 1, flags, C.byref(o) if o is not None else None)
+
+    assert call(ng=0) == -1 and call(ng=abi.ROULETTE_GROUPS_MAX + 1) == -1
+    for bad in (-1, NG):
+        gb = np.array(g)
+        gb[128] = bad
+        assert call(gt=gb) == -1
+    assert call(gt=None) == -1 and call(wt=None) == -1 and call(o=None) == -1
+    for mc in (-1, 0, 1, abi.SPLIT_COPIES_MAX + 1):
+        assert call(mc=mc) == -1
+    for flags in (2, 3, -1, 1 << 16):
+        assert call(flags=flags) == -1
+    with pytest.raises(C2DError) as err:
+        eng.census_split(g, NG, w, 1, 1)
+    assert err.value.code == -1 and "max_copies" in str(err.value)
+    assert eng.census_count() == 500
+    same_census(eng.census(), pre)
+
+
+def test_lost_census_is_a_state_error():
+    """The census lost as in test_gpu_census_restart.py test_chunked_census_lost_after_failed_step."""
+    gc = GoldenCase("ssc_tau")
+    with Engine(gc.grid(comtot_mode=abi.COMTOT_EXACT, census_inplace=1)) as e:
+        e.transport_step(gc.step_inputs(0))
+        d6, i5, keys = e.census()
+    g = SC.group_table(NG)
+    with Engine(gc.grid(comtot_mode=abi.COMTOT_EXACT, census_inplace=1, queue_capacity=1)) as e:
+        e.import_census(d6, i5, keys)
+        with pytest.raises(C2DError) as err:
+            e.transport_step(gc.step_inputs(1))
+        assert err.value.code == -5 and e.census_count() == 0
+        w = np.ones((e.nz, e.nr, NG))
+        for dry in (False, True):
+            with pytest.raises(C2DError) as err:
+                e.census_split(g, NG, w, MC, 0, dry_run=dry)
+            assert err.value.code == abi.C2D_E_STATE
+        with pytest.raises(C2DError) as err:                      # the arguments are judged first
+            e.census_split(g, NG, w, 65, 0)
+        assert err.value.code == -1
+        e.import_census(d6, i5, keys)
+        assert e.census_split(g, NG, w * 0.0, MC, 0)["n_after"] == len(keys)
+
+
+# --------------------------------------------------- 7. the census still runs
+def one_step(wl):
+    """One volume source per zone, carrying the zone's whole emission (ncycle 1: a step of
+    ncycle 0 writes no escape events)."""
+    nc, t = wl.clock(1)
+    return dataclasses.replace(wl.step0, ncycle=nc, time=t, nsv=np.ones((NZ, NR), np.int32),
+                               ewsv=np.array(wl.step0.Eloss_tot))
+
+
+@pytest.mark.parametrize("inplace", [0, 1])
+def test_census_runs_after_split(pool, inplace):
+    d6, i5, keys, g, w = pool
+    step = one_step(workload())
+    want = PC.split_numpy(d6, i5, keys, NZ, NR, g, NG, w, MC, 21)[2]
+    res = []
+    for split in (True, False):
+        with Engine(grid_of(inplace, abi.COMTOT_EXACT, capacity=1 << 16)) as e:
+            if split:
+                e.import_census(d6, i5, keys)
+                assert e.census_split(g, NG, w, MC, 21)["n_after"] == len(want[2])
+            else:                                   # the yardstick's census into a fresh context
+                e.import_census(*want)
+            e.transport_step(step)
+            ev = e.events()
+            res.append((np.sort(e.census()[2]), ev[np.lexsort(ev.T[::-1])], e.tallies()))
+    (k_a, ev_a, t_a), (k_b, ev_b, t_b) = res
+    assert len(k_a) > 0 and len(ev_a) > 0 and ev_a.shape == ev_b.shape
+    np.testing.assert_array_equal(k_a, k_b)
+    np.testing.assert_array_equal(ev_a.view(np.uint64), ev_b.view(np.uint64))
+    for k in TALLY_KEYS:
+        a, b = np.asarray(t_a[k]), np.asarray(t_b[k])
+        np.testing.assert_allclose(a, b, rtol=1e-12, atol=1e-12 * max(float(np.abs(b).max()), 0.0), err_msg=k)
+
+
+# ---------------------------------------------------------------- 8. sharding
+def test_sharded_union_equals_single_context(pool):
+    d6, i5, keys, _, _ = pool
+    g, ng = SC.group_table(4), 4
+    with Engine(grid_of(1, abi.COMTOT_EXACT)) as one:
+        one.import_census(d6, i5, keys)
+        count, energy = one.census_stats(g, ng)
+        w = PC.weight_ceiling(count, energy, 2.0)
+        assert (w > 0).any()
+        out = one.census_split(g, ng, w, MC, 5)
+        single = by_key(*one.census())
+    assert out["n_after"] > len(keys)
+    parts, c_sum, e_sum = [], np.zeros_like(count), np.zeros_like(energy)
+    shards = [Engine(grid_of(r, abi.COMTOT_EXACT)) for r in (0, 1)]
+    try:
+        for r, e in enumerate(shards):
+            e.import_census(d6[r::2], i5[r::2], keys[r::2])
+            c, en = e.census_stats(g, ng)
+            c_sum += c
+            e_sum += en
+        np.testing.assert_array_equal(c_sum, count)
+        w2 = PC.weight_ceiling(c_sum, e_sum, 2.0)            # once, from the summed statistics
+        np.testing.assert_array_equal(w2, w)                  # the power-of-two ceilings absorb the sums' last bits
+        for e in shards:
+            e.census_split(g, ng, w2, MC, 5)
+            parts.append(e.census())
+    finally:
+        for e in shards:
+            e.close()
+    union = by_key(*[np.concatenate([p[i] for p in parts]) for i in range(3)])
+    same_census(union, single)
+    same_census(single, by_key(*PC.split_numpy(d6, i5, keys, NZ, NR, g, ng, w, MC, 5)[2]))
+
+
+# --------------------------------------------------------------- 9. interplay
+def test_roulette_then_split_with_one_salt(eng, pool):
+    """Roulette, then split, the same census and the same salt: the yardsticks applied in that
+    order.  The two tags are independent on the device too."""
+    d6, i5, keys, g, w = pool
+    salt = 33
+    floors = np.where(np.isfinite(w) & (w > 0), w / 16.0, w)             # the window [W / 16, W]
+    eng.import_census(d6, i5, keys)
+    pre = eng.census()
+    r = eng.census_roulette(g, NG, floors, salt)
+    s = eng.census_split(g, NG, w, MC, salt)
+    keep, ew_r = PC.roulette_numpy(pre[0], pre[1], pre[2], NZ, NR, g, NG, floors, salt)
+    mid = pre[0][keep].copy()
+    mid[:, 4] = ew_r[keep]
+    want = PC.split_numpy(mid, pre[1][keep], pre[2][keep], NZ, NR, g, NG, w, MC, salt)[2]
+    assert r["n_after"] == keep.sum() < len(keys) and s["n_before"] == r["n_after"]
+    assert s["n_after"] == len(want[2]) > s["n_before"]
+    same_census(by_key(*eng.census()), by_key(*want))                      # the roulette's order is free
+
+
+# ------------------------------------------------- 10. unbiased in transport
+ENSEMBLE = 32
+ENSEMBLE_SEED = 4000
+
+
+def ensemble_census(d6, i5, keys, s, k, seed=None):
+    seed = ENSEMBLE_SEED if seed is None else seed
+    """Member s of an ensemble: the pool with its keys remixed, multiplied k-fold by the yardstick (k > 1)."""
+    kk = keys ^ np.uint64(PC.mix64_int(seed + s))
+    if k == 1:
+        return d6, i5, kk
+    g1, ng1, w1 = PC.multiply_tables(NZ, NR)
+    return PC.split_numpy(d6, i5, kk, NZ, NR, g1, ng1, w1, k, s)[2]
+
+
+def totals(tallies, events, k):
+    """The totals of edep, ecens and edout, and the number of escape events scaled by the copies'
+    weight 1 / k."""
+    return np.array([float(np.sum(tallies["edep"])), float(np.sum(tallies["ecens"])),
+                     float(np.sum(tallies["edout"])), len(events) / float(k)])
+
+
+def z_values(a, b):
+    """z of the difference of the two ensembles' means, and var_B / var_A, per total."""
+    va, vb = a.var(axis=0, ddof=1), b.var(axis=0, ddof=1)
+    return (a.mean(axis=0) - b.mean(axis=0)) / np.sqrt(va / len(a) + vb / len(b)), vb / va
+
+
+def scatter_step(wl):
+    """A step that carries the census alone (no sources, so the totals are the census's and a
+    wrong copy weight shows in them) through a plasma 100 times as dense as the workload's: at
+    the workload's own density the 3x3 grid is so thin that a census packet's step does not
+    depend on its random numbers at all, and the two ensembles would differ by rounding only."""
+    nc, t = wl.clock(1)
+    return dataclasses.replace(wl.step0, ncycle=nc, time=t, nsv=np.zeros((NZ, NR), np.int32),
+                               n_e=np.array(wl.step0.n_e) * 100.0)
+
+
+def test_split_is_unbiased_in_transport(pool):
+    """Two ensembles of 32 one-step runs from the pool, keys remixed per member: A unsplit, B
+    multiplied 4-fold on the device.  The totals of edep, ecens and edout and the number of
+    escape events scaled by the copies' weight (1 for A, 1/4 for B) agree within 4 standard
+    errors of their difference.
+
+    The weighted totals are heavy-tailed: a single Compton up-scattering off a relativistic
+    electron can outweigh the rest of a member, and B, with four times the histories, meets such
+    events more often.  The same ensembles were evaluated beforehand with the CPU oracle in
+    lineage mode (whose histories the exact build repeats bit for bit), the yardstick doing the
+    multiplication, for ENSEMBLE_SEED = 1000, 2000, ..., 6000: all six pass with |z| <= 2.0.
+    4000 is kept because no single event dominates its edout (var_B / var_A = 0.144), so a copy
+    weight of ew instead of ew / m, which moves every weighted total by a factor of 4, would
+    stand 50 standard errors off there.  The oracle's figures for it: z = -0.905, -0.909,
+    0.478, -0.230 and var_B / var_A = 27.7, 27.8, 0.144, 0.546; the first run on the device:
+    z = -0.905, -0.909, 0.477, -0.343 and var_B / var_A = 27.7, 27.8, 0.144, 0.572 (the tallies
+    to the digits shown; why the escape counts differ in the second digit was not looked into)."""
+    d6, i5, keys, _, _ = pool
+    step = scatter_step(workload())
+    a, b = np.zeros((ENSEMBLE, 4)), np.zeros((ENSEMBLE, 4))
+    with Engine(grid_of(1, abi.COMTOT_EXACT, capacity=1 << 16)) as e:
+        for s in range(ENSEMBLE):
+            for k, res in ((1, a), (4, b)):
+                e.import_census(*ensemble_census(d6, i5, keys, s, 1))
+                if k > 1:
+                    out = PC.multiply(e, k, s)
+                    assert out["n_after"] == out["n_before"] + 3 * out["n_split"]
+                e.transport_step(step)
+                res[s] = totals(e.tallies(), e.events(), k)
+    z, ratio = z_values(a, b)
+    print("z (edep, ecens, edout, escapes / k):", np.round(z, 3), "var_B / var_A:", np.round(ratio, 3))
+    assert np.all(a.mean(axis=0) > 0)
+    assert np.all(np.abs(z) <= 4.0)
+
+
+# ------------------------------------------------ 11. CoupledRun with a ceiling
+def c3_small(sources=3000):
+    deck = dict(synth.C3_DECK, nz=NZ, nr=NR, T_const=1)
+    return synth.c3_workload(sources=sources, comtot_mode=abi.COMTOT_TABLE, census_capacity=1 << 18,
+                             event_capacity=1 << 18, deck=deck)
+
+
+def coupled_rows(ctl_of, steps=6, cut=None, tmp_path=None):
+    """Rows of `steps` steps and the final census keys; ctl_of(n): the census control of step n;
+    cut: save after that many steps and carry on in a fresh context."""
+    wl = c3_small()
+    eng = Engine(dataclasses.replace(wl.grid, census_inplace=1))
+    try:
+        run = CoupledRun(eng, wl, census_control=ctl_of(0))
+        rows = []
+        for n in range(steps):
+            if cut is not None and n == cut:
+                p = tmp_path / "cut.ckpt"
+                run.save(p)
+                eng.close()
+                wl = c3_small()
+                eng = Engine(dataclasses.replace(wl.grid, census_inplace=1))
+                run = CoupledRun.restore(eng, wl, p, census_control=ctl_of(n))
+            run.census_control = ctl_of(n)
+            rows.append(dict(run.step()))
+        return rows, np.sort(eng.census()[2])
+    finally:
+        eng.close()
+
+
+def split_rows(rows):
+    return [(r["census_before"], r["census_after"], r.get("split_copies"), r.get("split_skipped")) for r in rows]
+
+
+def test_coupled_run_with_a_ceiling(tmp_path):
+    """c3_small, 6 steps.  Its sources all carry one weight and absorption only lightens a packet,
+    so under one CensusControl(target, ceiling_ratio=4) no record ever stands above 4 times its
+    (cell, group)'s mean (measured: max ew / group mean < 1.5 in every step and no split for
+    targets of 1/2 to 1/16 of the free census, with or without the roulette running, whose
+    survivors all end at one weight).  The heavy tail the ceiling is for is made the way the
+    roulette makes it: three steps held to 1/64 of the free census leave about a hundred
+    survivors of 32 to 64 times a source's weight; then the target is lifted to twice the free
+    census and the ceiling switched on, fresh packets dilute the groups' means, and the survivors
+    stand above 4 times those means."""
+    free, keys_free = coupled_rows(lambda n: None)
+    n6 = len(keys_free)
+    assert n6 > 2000
+    # without a ceiling the rows are today's: no split_* keys, and a control that never acts changes nothing
+    plain, keys_plain = coupled_rows(lambda n: PC.CensusControl(target=2 * n6))
+    assert all(set(r) - set(f) == {"census_before", "census_after", "roulette_ms"} for r, f in zip(plain, free))
+    assert all(r["census_after"] == r["census_before"] and r["roulette_ms"] == 0 for r in plain)
+    np.testing.assert_array_equal(keys_plain, keys_free)
+    tight = PC.CensusControl(target=n6 // 64)
+    ctl = PC.CensusControl(target=2 * n6, ceiling_ratio=4, max_copies=8)
+    ctl_of = lambda n: tight if n < 3 else ctl
+    rows, keys_a = coupled_rows(ctl_of)
+    limit = ctl.target * (1.0 + ctl.slack)
+    print(split_rows(rows), "targets", tight.target, ctl.target)
+    assert not any(k.startswith("split_") for r in rows[:3] for k in r)
+    assert all({"split_copies", "split_ms", "split_skipped"} <= set(r) for r in rows[3:])
+    assert any(r["split_copies"] > 0 for r in rows[3:])
+    assert all(r["census_after"] == r["census_before"] + r["split_copies"] and r["roulette_ms"] == 0 for r in rows[3:])
+    assert all(r["census_after"] <= limit for r in rows[3:] if r["split_copies"] > 0)
+    assert all(r["split_copies"] == 0 for r in rows[3:] if r["split_skipped"])
+    assert len(keys_a) == rows[-1]["census_after"] and len(np.unique(keys_a)) == len(keys_a)
+    rows_b, keys_b = coupled_rows(ctl_of)
+    np.testing.assert_array_equal(keys_a, keys_b)
+    assert split_rows(rows) == split_rows(rows_b)
+    for cut in (2, 4):                                             # before and after the first split
+        _, keys_c = coupled_rows(ctl_of, cut=cut, tmp_path=tmp_path)
+        np.testing.assert_array_equal(keys_a, keys_c)
