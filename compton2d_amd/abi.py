@@ -590,6 +590,10 @@ class FpCall:
 OBS_SED, OBS_LC = 0, 1
 OBS_MAX_T, OBS_MAX_MU, OBS_MAX_E = 1024, 32, 256
 OBS_SET_MAX = 8                 # C2D_OBS_SET_MAX: members of an observer set (c2d_obs_set_*)
+# the exported state of an exact member (c2d_obs_set_state): head words, words per bin
+OBS_STATE_HEAD_WORDS, OBS_STATE_BIN_WORDS = 8, 5
+OBS_STATE_MAGIC = 0x005853424F443243            # "C2DOBSX\0"
+OBS_EXACT_E_MIN, OBS_EXACT_E_MAX, OBS_EXACT_BITS = -469, 489, 84
 
 
 class ObsBins(C.Structure):

@@ -227,13 +227,29 @@ class CoupledRun:
         return self.state["f_nt"], self.state["Pnt"]
 
     # -- checkpoints ---------------------------------------------------------
-    def save(self, path) -> int:
+    def _observer_members(self) -> int:
+        """Members of the engine's observer set."""
+        from .engine import C2DError
+        n = 0
+        while n < abi.OBS_SET_MAX:
+            try:
+                self.eng.obs_set_shape(n)
+            except C2DError:
+                break
+            n += 1
+        return n
+
+    def save(self, path, observer_set: bool = False) -> int:
         """Save the run between two steps (Engine.checkpoint_write): the
         context's census, kappa_prev, device electrons and FP flags, and as
         the user blob an .npz (no pickling) of the step number, ecens_prev,
         the zone scalars of `state` (f_nt / Pnt too while they live on the
         host) and the workload's nst, dt and seed.  Returns the census
-        records written.  Observer accumulations are not part of it."""
+        records written.  observer_set: the engine's exact observer set
+        (Engine.obs_set_exact) travels too, every member's state as a further
+        member of the blob (obs_state_<id>), for restore(observer_set=True);
+        without it the blob is what it always was, and observer accumulations
+        are not part of the checkpoint."""
         import io
         import zipfile
         on_dev = self._electrons_on_device()
@@ -244,6 +260,11 @@ class CoupledRun:
             if on_dev and k in ("f_nt", "Pnt"):
                 continue
             blob["state_" + k] = np.asarray(v)
+        if observer_set:
+            m = self._observer_members()
+            blob["obs_members"] = np.int64(m)
+            for i in range(m):
+                blob["obs_state_%d" % i] = self.eng.obs_set_state(i)
         # an .npz with fixed member dates: the same state gives the same bytes
         buf = io.BytesIO()
         with zipfile.ZipFile(buf, "w", zipfile.ZIP_STORED) as z:
@@ -254,12 +275,34 @@ class CoupledRun:
         return self.eng.checkpoint_write(path, buf.getvalue())
 
     @classmethod
-    def restore(cls, eng: Engine, wl: CoupledWorkload, path, **kw) -> "CoupledRun":
+    def restore(cls, eng: Engine, wl: CoupledWorkload, path, observer_set: bool = False, **kw) -> "CoupledRun":
         """A run on `eng` (a fresh context of the workload's grid) that
         carries on where save() stopped: step() runs step n.  kw: the
-        constructor's arguments; device_resident must be the saved run's."""
+        constructor's arguments; device_resident must be the saved run's.
+        observer_set: the states saved by save(observer_set=True) are merged
+        into the exact observer set the caller has re-created on `eng` (the
+        same members in the same order, the same w_max): the set then holds
+        the saved integers, bit for bit.  ValueError if the checkpoint has no
+        states, another number of them, or one of another binning or bound."""
         import io
+        from .engine import C2DError
         run = cls(eng, wl, **kw)
+        states = []
+        if observer_set:                               # checked before the engine reads anything
+            from . import checkpoint, observer
+            with np.load(io.BytesIO(checkpoint.read_user(path)), allow_pickle=False) as z:
+                if "obs_members" not in z.files:
+                    raise ValueError("checkpoint '%s' was saved without the observer set" % path)
+                states = [np.array(z["obs_state_%d" % i], np.uint64) for i in range(int(z["obs_members"]))]
+            if len(states) != run._observer_members():
+                raise ValueError("checkpoint '%s' holds %d observer states, the engine's set has %d members"
+                                 % (path, len(states), run._observer_members()))
+            for i, st in enumerate(states):
+                try:
+                    observer.state_merge(eng.obs_set_state(i), st)
+                except C2DError as err:
+                    raise ValueError("checkpoint '%s': observer state %d does not fit member %d: %s"
+                                     % (path, i, i, err)) from None
         _, user = eng.checkpoint_read(path)
         with np.load(io.BytesIO(user), allow_pickle=False) as z:
             if (not np.array_equal(z["wl_nst"], np.asarray(wl.nst)) or float(z["wl_dt"]) != float(wl.dt)
@@ -272,4 +315,6 @@ class CoupledRun:
             for k in z.files:
                 if k.startswith("state_"):
                     run.state[k[len("state_"):]] = np.array(z[k], copy=True)
+        for i, st in enumerate(states):
+            eng.obs_set_merge(i, st)
         return run

@@ -78,7 +78,14 @@ struct ObsHist {
   std::vector<double> edges;                  /* t0 t1 mu0 mu1 E0 E1 */
   double* hist = nullptr;                     /* device F | F2 | count: 3 x n_t x n_mu x n_e */
   double* red = nullptr;                      /* world_sum reduction buffer, same size (decks only) */
+  /* an exact set's member (c2d_obs_set_exact): its integer accumulators on
+   * the device, 5 u64 a bin in the state's order and then n_rejected, and
+   * (decks only) the world_sum buffer of their 32-bit halves */
+  uint64_t* acc = nullptr;
+  uint64_t* acc_red = nullptr;
+  int32_t e = 0;                              /* the exponent bound */
   size_t nh() const { return (size_t)n_t * n_mu * n_e; }
+  size_t acc_words() const { return 5 * nh() + 1; }
 };
 
 /* what the single observer and the set each keep about their launches */
@@ -112,6 +119,9 @@ struct ObsState {
   double* set_edges = nullptr;                /* every member's edges, in the plan's LDS order */
   bool set_started = false;                   /* accumulated since the last clear */
   ObsLaunches set_l;
+  bool set_exact = false;                     /* c2d_obs_set_exact since the last clear */
+  double set_wmax = 0.0;
+  ObsExactDev set_x = {};
 };
 
 struct c2d_ctx;

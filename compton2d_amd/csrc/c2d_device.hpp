@@ -506,6 +506,13 @@ struct ObsSetDev {
   ObsSetMember m[OBS_SET_MAX];
 };
 
+/* the exact set (obsacc.hip c2d_obs_set_exact_kernel) beside an ObsSetDev
+ * whose plan counts 5 u64 words per privatised bin and whose members' F
+ * point at their integer accumulators (5 words a bin, then n_rejected) */
+struct ObsExactDev {
+  int32_t e[OBS_SET_MAX];                    /* the members' exponent bounds (c2d_obsacc.h) */
+};
+
 }  // namespace c2d
 
 #endif

@@ -11,11 +11,15 @@
 #include <cstdlib>
 
 #include "c2d_ctx.hpp"
+#include "c2d_obsacc_host.h"
 
 extern "C" int c2d_launch_obs_segs(const ObsDev* O, const double* const* ev, const int64_t* n, int nseg,
                                    int grid, hipStream_t stream);
 extern "C" int c2d_launch_obs_set(const ObsSetDev* Q, const double* const* ev, const int64_t* n, int nseg,
                                   int grid, hipStream_t stream);
+extern "C" int c2d_launch_obs_set_exact(const ObsSetDev* Q, const ObsExactDev* X, const double* const* ev,
+                                        const int64_t* n, int nseg, int grid, hipStream_t stream);
+extern "C" int c2d_launch_obs_merge(uint64_t* acc, const uint64_t* add, int64_t nbins, uint64_t rej, hipStream_t stream);
 extern "C" size_t c2d_obs_lds_bytes(int n_t, int n_mu, int n_e, int lds_rows);
 extern "C" int c2d_obs_block(void);
 
@@ -55,6 +59,8 @@ int obs_settle(c2d_ctx* c) {
 static void obs_hist_free(ObsHist& h) {
   if (h.hist) (void)hipFree(h.hist);
   if (h.red) (void)hipFree(h.red);
+  if (h.acc) (void)hipFree(h.acc);
+  if (h.acc_red) (void)hipFree(h.acc_red);
   h = ObsHist{};
 }
 
@@ -66,6 +72,9 @@ static void obs_set_free(ObsState& o) {
   o.set = ObsSetDev{};
   o.set_started = false;
   o.set_l = ObsLaunches{};
+  o.set_exact = false;
+  o.set_wmax = 0.0;
+  o.set_x = ObsExactDev{};
 }
 
 void obs_release(c2d_ctx* c) {
@@ -93,13 +102,6 @@ static int obs_bins_check(c2d_ctx* c, const c2d_obs_bins* b, const char* who) {
   if (b->mode == C2D_OBS_SED && b->n_mu != 1)
     return fail(c, C2D_E_ARG, "%s: the SED mode has one angular window", who);
   return C2D_OK;
-}
-
-/* lo[] and hi[] non-decreasing: the kernel may search them by bisection */
-static int obs_sorted(const double* lo, const double* hi, int n) {
-  for (int i = 1; i < n; i++)
-    if (!(lo[i] >= lo[i - 1]) || !(hi[i] >= hi[i - 1])) return 0;
-  return 1;
 }
 
 /* what ObsDev and ObsSetMember say alike about a binning */
@@ -181,8 +183,9 @@ static int obs_launch(c2d_ctx* c, bool set, const double* const* ev, const int64
   ObsLaunches& l = set ? c->obs.set_l : c->obs.one_l;
   const int64_t bs = c2d_obs_block();
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->n_cu * l.wg_per_cu, (tot + bs - 1) / bs));
-  const int rc = set ? c2d_launch_obs_set(&c->obs.set, ev, m, nseg, grid, stream)
-                     : c2d_launch_obs_segs(&c->obs.dev, ev, m, nseg, grid, stream);
+  const int rc = !set                ? c2d_launch_obs_segs(&c->obs.dev, ev, m, nseg, grid, stream)
+                 : c->obs.set_exact ? c2d_launch_obs_set_exact(&c->obs.set, &c->obs.set_x, ev, m, nseg, grid, stream)
+                                    : c2d_launch_obs_set(&c->obs.set, ev, m, nseg, grid, stream);
   if (rc) return fail(c, C2D_E_HIP, "%s launch: %s", set ? "obs set" : "obs", hipGetErrorString((hipError_t)rc));
   l.launches++;
   return C2D_OK;
@@ -307,6 +310,71 @@ static int obs_download(c2d_ctx* c, const ObsHist& h, double* F, double* F2, dou
   return C2D_OK;
 }
 
+/* ---- an exact member's integers on the host ---- */
+static int obs_exact_download(c2d_ctx* c, const ObsHist& h, std::vector<uint64_t>& a) {
+  a.resize(h.acc_words());
+  HIPCHK(c, hipMemcpy(a.data(), h.acc, a.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return C2D_OK;
+}
+
+/* a (the accumulators of one member, n_rejected last) summed over the
+ * context's communicator: every word travels as two 32-bit halves in u64
+ * containers (ncclSum cannot carry between words; 2^32 ranks fit), then the
+ * carries are normalised limb by limb on the host */
+static int obs_exact_world_sum(c2d_ctx* c, const ObsHist& h, std::vector<uint64_t>& a, const char* who) {
+  const size_t n = a.size(), nh = h.nh();
+  std::vector<uint64_t> half(2 * n);
+  for (size_t i = 0; i < n; i++) {
+    half[2 * i] = a[i] & 0xffffffffull;
+    half[2 * i + 1] = a[i] >> 32;
+  }
+  uint64_t* w = h.acc_red;
+  HIPCHK(c, hipMemcpyAsync(w, half.data(), 2 * n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  const ncclResult_t r = ncclAllReduce(w, w, 2 * n, ncclUint64, ncclSum, c->comm, c->stream);
+  if (r != ncclSuccess) return fail(c, C2D_E_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
+  HIPCHK(c, hipMemcpyAsync(half.data(), w, 2 * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  /* the integers: F and F2 are 4 halves each, count and n_rejected 2 */
+  uint64_t over = 0;
+  const auto norm = [&](size_t word, int words) {
+    uint64_t carry = 0;
+    for (int k = 0; k < 2 * words; k++) {
+      const uint64_t t = half[2 * word + k] + carry;     /* below 2^64: a half-sum is below 2^64 - 2^32 */
+      half[2 * word + k] = t & 0xffffffffull;
+      carry = t >> 32;
+    }
+    over |= carry;
+    for (int k = 0; k < words; k++) a[word + k] = half[2 * (word + k)] | (half[2 * (word + k) + 1] << 32);
+  };
+  for (size_t b = 0; b < nh; b++) {
+    norm(C2D_OA_BIN_WORDS * b, 2);
+    norm(C2D_OA_BIN_WORDS * b + 2, 2);
+    norm(C2D_OA_BIN_WORDS * b + 4, 1);
+  }
+  norm(C2D_OA_BIN_WORDS * nh, 1);
+  if (over) return fail(c, C2D_E_ARG, "%s: a sum over the communicator carries out of its top bit", who);
+  return C2D_OK;
+}
+
+static int obs_exact_rejected(c2d_ctx* c, uint64_t n_rejected, const char* who) {
+  if (!n_rejected) return C2D_OK;
+  return fail(c, C2D_E_NONFINITE,
+              "%s: %llu events were rejected (a boosted weight NaN, negative or not below the bound of w_max = %g); "
+              "the sums lack them",
+              who, (unsigned long long)n_rejected, c->obs.set_wmax);
+}
+
+/* F | F2 | count of an exact member as rounded doubles in v (3 nh) */
+static int obs_exact_values(c2d_ctx* c, const ObsHist& h, const char* who, int32_t world_sum, double* F, double* F2,
+                            double* count) {
+  std::vector<uint64_t> a;
+  OBSCHK(obs_exact_download(c, h, a));
+  if (world_sum) OBSCHK(obs_exact_world_sum(c, h, a, who));
+  OBSCHK(obs_exact_rejected(c, a[a.size() - 1], who));
+  c2d_oa_bins_doubles(a.data(), h.e, (int64_t)h.nh(), F, F2, count);
+  return C2D_OK;
+}
+
 /* The tool's files of a deck's histogram so far (postprocessing/pspt.c:323-353,
  * plcm.c:466-552).  world_sum: summed over the context's communicator first
  * (every rank calls, rank 0 writes). */
@@ -316,8 +384,11 @@ static int obs_write(c2d_ctx* c, const ObsHist& h, const char* who, const char* 
   OBSCHK(obs_settle(c));
   const size_t nh = h.nh();
   std::vector<double> v(3 * nh);
-  if (world_sum) {
-    if (!c->comm) return fail(c, C2D_E_STATE, "%s: world_sum needs c2d_comm_init", who);
+  if (world_sum && !c->comm) return fail(c, C2D_E_STATE, "%s: world_sum needs c2d_comm_init", who);
+  if (h.acc) {                                  /* a member of an exact set: its integers, rounded once */
+    OBSCHK(obs_exact_values(c, h, who, world_sum, v.data(), v.data() + nh, v.data() + 2 * nh));
+    if (world_sum && c->comm_rank != 0) return C2D_OK;
+  } else if (world_sum) {
     double* w = h.red;
     HIPCHK(c, hipMemcpyAsync(w, h.hist, 3 * nh * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     const ncclResult_t r = ncclAllReduce(w, w, 3 * nh, ncclDouble, ncclSum, c->comm, c->stream);
@@ -432,8 +503,10 @@ extern "C" int c2d_obs_write_pspt(c2d_ctx* c, const char* path, int32_t factor, 
  * privatised leading time rows.  What the edges leave of the workgroup's
  * OBS_SET_LDS is shared out equally among the members, each taking whole
  * rows of its share (at most its n_t); what that leaves over is handed out
- * in registration order.  -1 when the edges alone do not fit. */
-static int obs_set_plan(ObsSetDev& Q, int* wg_per_cu) {
+ * in registration order.  -1 when the edges alone do not fit.  bin_words: the
+ * LDS words of a privatised bin, 3 doubles (F, F2, count) or the exact set's
+ * 5 u64 (c2d_obsacc.h). */
+static int obs_set_plan(ObsSetDev& Q, int* wg_per_cu, int bin_words = 3) {
   const int64_t budget = (OBS_SET_LDS - OBS_SET_LDS_STATIC) / (int64_t)sizeof(double);
   int64_t ne = 0;
   for (int j = 0; j < Q.n; j++) {
@@ -444,13 +517,13 @@ static int obs_set_plan(ObsSetDev& Q, int* wg_per_cu) {
   int64_t left = budget - ne;
   const int64_t share = Q.n ? left / Q.n : 0;
   for (int j = 0; j < Q.n; j++) {
-    const int64_t row = 3 * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
+    const int64_t row = bin_words * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
     Q.m[j].lds_rows = (int32_t)std::min<int64_t>(Q.m[j].n_t, share / row);
     left -= Q.m[j].lds_rows * row;
   }
   int64_t nh = 0;
   for (int j = 0; j < Q.n; j++) {
-    const int64_t row = 3 * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
+    const int64_t row = bin_words * (int64_t)Q.m[j].n_mu * Q.m[j].n_e;
     const int64_t more = std::min<int64_t>(Q.m[j].n_t - Q.m[j].lds_rows, left / row);
     Q.m[j].lds_rows += (int32_t)more;
     left -= more * row;
@@ -463,6 +536,29 @@ static int obs_set_plan(ObsSetDev& Q, int* wg_per_cu) {
   const size_t bytes = (size_t)(ne + nh) * sizeof(double) + OBS_SET_LDS_STATIC;
   *wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / bytes));
   return 0;
+}
+
+/* ---- the exact set (c2d_obs_set_exact; c2d_obsacc.h, obsacc.hip) ---- */
+static int obs_exact_bound(c2d_ctx* c, double w_max, double G, int32_t* e, const char* who) {
+  if (c2d_oa_bound(w_max, G, e)) return C2D_OK;
+  return fail(c, C2D_E_ARG, "%s: w_max %g and Gamma %g give no exponent bound within [%d, %d]", who, w_max, G,
+              C2D_OA_E_MIN, C2D_OA_E_MAX);
+}
+
+/* h's zeroed integer accumulators (and a deck's world_sum buffer: twice the
+ * words, 32-bit halves in u64 containers); on failure h keeps neither */
+static int obs_exact_alloc(c2d_ctx* c, ObsHist& h, int32_t e, const char* who) {
+  hipError_t r = dalloc(&h.acc, h.acc_words());
+  if (r == hipSuccess && h.kind != OBS_RAW) r = dalloc(&h.acc_red, 2 * h.acc_words());
+  if (r == hipSuccess) r = hipMemset(h.acc, 0, h.acc_words() * sizeof(uint64_t));
+  if (r == hipSuccess) {
+    h.e = e;
+    return C2D_OK;
+  }
+  if (h.acc) (void)hipFree(h.acc);
+  if (h.acc_red) (void)hipFree(h.acc_red);
+  h.acc = h.acc_red = nullptr;
+  return fail(c, C2D_E_HIP, "%s: %s", who, hipGetErrorString(r));
 }
 
 extern "C" int c2d_obs_set_clear(c2d_ctx* c) {
@@ -486,8 +582,10 @@ static int obs_set_add_member(c2d_ctx* c, const c2d_obs_bins* b, ObsHist&& h, in
   ObsSetMember& M = Q.m[Q.n++];
   M = ObsSetMember{};
   obs_describe(M, b);
+  int32_t e = 0;
+  if (o.set_exact) OBSCHK(obs_exact_bound(c, o.set_wmax, b->gam_bulk, &e, who));
   int wg = 1;
-  if (obs_set_plan(Q, &wg))
+  if (obs_set_plan(Q, &wg, o.set_exact ? C2D_OA_BIN_WORDS : 3))
     return fail(c, C2D_E_ARG, "%s: the set's bin edges (%lld B with this member) exceed the workgroup's %d B of LDS",
                 who, (long long)(sizeof(double) * (2 * ((int64_t)b->n_t + b->n_mu + b->n_e) + o.set.n_edges)),
                 OBS_SET_LDS - OBS_SET_LDS_STATIC);
@@ -499,9 +597,21 @@ static int obs_set_add_member(c2d_ctx* c, const c2d_obs_bins* b, ObsHist&& h, in
   for (const ObsHist& m : o.set_h) all.insert(all.end(), m.edges.begin(), m.edges.end());
   double* d_edges = nullptr;
   OBSCHK(obs_hist_make(c, b, h, all, &d_edges, who));
+  if (o.set_exact) {
+    const int rc = obs_exact_alloc(c, h, e, who);
+    if (rc != C2D_OK) {
+      (void)hipFree(d_edges);
+      obs_hist_free(h);
+      return rc;
+    }
+  }
   if (o.set_edges) (void)hipFree(o.set_edges);
   Q.edges = o.set_edges = d_edges;
   obs_point(M, h);
+  if (o.set_exact) {
+    M.F = reinterpret_cast<double*>(h.acc);   /* what the exact kernel accumulates into */
+    o.set_x.e[Q.n - 1] = e;
+  }
   if (id) *id = Q.n - 1;
   o.set = Q;
   o.set_l.wg_per_cu = wg;
@@ -568,6 +678,7 @@ extern "C" int c2d_obs_set_result(c2d_ctx* c, int32_t id, double* F, double* F2,
   OBSCHK(obs_set_member(c, id, "c2d_obs_set_result", &h));
   HIPCHK(c, hipSetDevice(c->cfg.device));
   OBSCHK(obs_settle(c));
+  if (h->acc) return obs_exact_values(c, *h, "c2d_obs_set_result", 0, F, F2, count);
   return obs_download(c, *h, F, F2, count);
 }
 
@@ -586,4 +697,139 @@ extern "C" int c2d_obs_set_write(c2d_ctx* c, int32_t id, const char* path, int32
   if (h->kind == OBS_RAW)
     return fail(c, C2D_E_STATE, "c2d_obs_set_write: member %d was added without a deck", (int)id);
   return obs_write(c, *h, "c2d_obs_set_write", path, factor, world_sum);
+}
+
+/* ------------------------------------------------------------------ */
+/* exact sets: integer sums, their state, merge and the host twin      */
+/* ------------------------------------------------------------------ */
+extern "C" int c2d_obs_set_exact(c2d_ctx* c, double w_max) {
+  const char* who = "c2d_obs_set_exact";
+  if (!c) return C2D_E_ARG;
+  ObsState& o = c->obs;
+  if (!(w_max > 0.0) || !c2d_oa_finite(w_max)) return fail(c, C2D_E_ARG, "%s: w_max must be finite and positive", who);
+  if (o.set_started) return fail(c, C2D_E_STATE, "%s: the set has accumulated events; c2d_obs_set_clear first", who);
+  if (o.set_exact) return fail(c, C2D_E_STATE, "%s: the set is exact already; c2d_obs_set_clear first", who);
+  int32_t e[OBS_SET_MAX] = {0};
+  for (int j = 0; j < o.set.n; j++) OBSCHK(obs_exact_bound(c, w_max, o.set.m[j].gam_bulk, &e[j], who));
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  OBSCHK(obs_settle(c));
+  for (int j = 0; j < o.set.n; j++) {
+    const int rc = obs_exact_alloc(c, o.set_h[(size_t)j], e[j], who);
+    if (rc != C2D_OK) {                       /* the set stays as it was */
+      for (int k = 0; k < j; k++) {
+        ObsHist& h = o.set_h[(size_t)k];
+        (void)hipFree(h.acc);
+        if (h.acc_red) (void)hipFree(h.acc_red);
+        h.acc = h.acc_red = nullptr;
+      }
+      return rc;
+    }
+  }
+  ObsSetDev Q = o.set;
+  int wg = o.set_l.wg_per_cu;
+  (void)obs_set_plan(Q, &wg, C2D_OA_BIN_WORDS);   /* the edges fitted before: only the rows change */
+  for (int j = 0; j < Q.n; j++) {
+    Q.m[j].F = reinterpret_cast<double*>(o.set_h[(size_t)j].acc);
+    o.set_x.e[j] = e[j];
+  }
+  o.set = Q;
+  o.set_l.wg_per_cu = wg;
+  o.set_exact = true;
+  o.set_wmax = w_max;
+  return C2D_OK;
+}
+
+/* member `id` of an exact set, any binning in flight settled */
+static int obs_exact_member(c2d_ctx* c, int32_t id, const char* who, const ObsHist** h) {
+  OBSCHK(obs_set_member(c, id, who, h));
+  if (!c->obs.set_exact || !(*h)->acc) return fail(c, C2D_E_STATE, "%s: c2d_obs_set_exact first", who);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return obs_settle(c);
+}
+
+/* the member's state (include/compton2d.h) on the host */
+static int obs_exact_state(c2d_ctx* c, int32_t id, const ObsHist& h, std::vector<uint64_t>& s) {
+  std::vector<uint64_t> a;
+  OBSCHK(obs_exact_download(c, h, a));
+  const ObsSetMember& M = c->obs.set.m[id];
+  c2d_oa_head H;
+  H.mode = M.mode; H.n_t = h.n_t; H.n_mu = h.n_mu; H.n_e = h.n_e; H.e = h.e;
+  H.bins_digest = c2d_oa_bins_digest(M.gam_bulk, M.rmax, M.t_offset, h.edges.data(), h.edges.size());
+  H.n_rejected = a[a.size() - 1];
+  s.assign((size_t)H.words(), 0ull);
+  std::copy(a.begin(), a.end() - 1, s.begin() + C2D_OA_HEAD_WORDS);
+  H.payload_digest = c2d_oa_payload_digest(s.data(), H.nh());
+  c2d_oa_head_write(s.data(), H);
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_exact_info(c2d_ctx* c, int32_t id, int32_t* e, int64_t* n_rejected) {
+  const ObsHist* h = nullptr;
+  OBSCHK(obs_exact_member(c, id, "c2d_obs_set_exact_info", &h));
+  if (e) *e = h->e;
+  if (n_rejected) {
+    uint64_t r = 0;
+    HIPCHK(c, hipMemcpy(&r, h->acc + h->acc_words() - 1, sizeof r, hipMemcpyDeviceToHost));
+    *n_rejected = (int64_t)r;
+  }
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_state_words(c2d_ctx* c, int32_t id, int64_t* words) {
+  const ObsHist* h = nullptr;
+  OBSCHK(obs_exact_member(c, id, "c2d_obs_set_state_words", &h));
+  if (words) *words = C2D_OA_HEAD_WORDS + C2D_OA_BIN_WORDS * (int64_t)h->nh();
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_state(c2d_ctx* c, int32_t id, uint64_t* out, int64_t cap) {
+  const ObsHist* h = nullptr;
+  OBSCHK(obs_exact_member(c, id, "c2d_obs_set_state", &h));
+  std::vector<uint64_t> s;
+  OBSCHK(obs_exact_state(c, id, *h, s));
+  if (!out || cap < (int64_t)s.size())
+    return fail(c, C2D_E_ARG, "c2d_obs_set_state: the state has %lld words, the buffer %lld", (long long)s.size(),
+                (long long)cap);
+  std::copy(s.begin(), s.end(), out);
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_set_merge(c2d_ctx* c, int32_t id, const uint64_t* in, int64_t words) {
+  const char* who = "c2d_obs_set_merge";
+  const ObsHist* h = nullptr;
+  OBSCHK(obs_exact_member(c, id, who, &h));
+  if (!in) return fail(c, C2D_E_ARG, "%s: no state", who);
+  /* every check on the host, on a copy of the member's own state */
+  std::vector<uint64_t> cur;
+  OBSCHK(obs_exact_state(c, id, *h, cur));
+  const char* why = c2d_oa_state_add(cur.data(), (int64_t)cur.size(), in, words);
+  if (why) return fail(c, C2D_E_ARG, "%s: %s", who, why);
+  const int64_t nh = (int64_t)h->nh();
+  uint64_t* d = nullptr;
+  HIPCHK(c, dalloc(&d, (size_t)(C2D_OA_BIN_WORDS * nh)));
+  hipError_t r = hipMemcpyAsync(d, in + C2D_OA_HEAD_WORDS, (size_t)(C2D_OA_BIN_WORDS * nh) * sizeof(uint64_t),
+                                hipMemcpyHostToDevice, c->stream);
+  if (r == hipSuccess) r = (hipError_t)c2d_launch_obs_merge(h->acc, d, nh, in[6], c->stream);
+  const hipError_t rs = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  if (r == hipSuccess) r = rs;
+  if (r != hipSuccess) return fail(c, C2D_E_HIP, "%s: %s", who, hipGetErrorString(r));
+  c->obs.set_started = true;                  /* the set holds sums now: no further member */
+  return C2D_OK;
+}
+
+extern "C" int c2d_obs_exact_host(const c2d_obs_bins* bins, double w_max, const double* events, int64_t n,
+                                  uint64_t* state, int64_t cap) {
+  return c2d_oa_exact_host(bins, w_max, events, n, state, cap);
+}
+
+extern "C" int c2d_obs_state_merge(uint64_t* into, int64_t into_words, const uint64_t* from, int64_t from_words) {
+  return c2d_oa_state_add(into, into_words, from, from_words) ? C2D_E_ARG : C2D_OK;
+}
+
+extern "C" int c2d_obs_state_result(const uint64_t* state, int64_t words, double* F, double* F2, double* count) {
+  c2d_oa_head H;
+  if (c2d_oa_head_read(state, words, &H)) return C2D_E_ARG;
+  c2d_oa_bins_doubles(state + C2D_OA_HEAD_WORDS, H.e, H.nh(), F, F2, count);
+  return C2D_OK;
 }

@@ -21,16 +21,9 @@
  * several windows and light curves, c2d_obs_set_*) in one pass: the event
  * words and cos(phi) are shared, the members share the workgroup's LDS.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/compton2d.h"
-#include "c2d_device.hpp"
-#include "c2d_math.h"
+#include "c2d_observe.hpp"
 
 namespace c2d {
-
-constexpr int OBS_BLOCK = 512;
 
 __device__ inline double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -61,102 +54,6 @@ __device__ inline void agg_add(double* F, double* F2, double* C, int h, double w
   }
 }
 
-/* First k with lo[k] <= x < hi[k] (the tools' linear first-match scan), or n.
- * When lo[] and hi[] are both non-decreasing (`sorted`, checked on the host)
- * the matching k form a contiguous range whose first element is the first k
- * with hi[k] > x: a binary search then gives the same answer, NaN included. */
-__device__ inline int first_bin(const double* lo, const double* hi, int n, bool sorted, double x) {
-  if (!sorted) {
-    int k;
-    for (k = 0; k < n; k++)
-      if (x >= lo[k] && x < hi[k]) break;
-    return k;
-  }
-  int a = 0, b = n;                      /* first k in [a, b) with hi[k] > x */
-  while (a < b) {
-    const int m = (a + b) >> 1;
-    if (hi[m] > x) b = m; else a = m + 1;
-  }
-  return (a < n && x >= lo[a]) ? a : n;
-}
-
-/* the event segments of one launch (the transport's event shards, back to
- * back): event e lies in segment s with pre[s] <= e < pre[s + 1] */
-struct ObsSegs {
-  const double* base[C2D_EV_SHARDS];
-  int64_t pre[C2D_EV_SHARDS + 1];
-  int32_t nseg;
-};
-
-/* ---- event fetch: the segment table in LDS, then one event's words ---- */
-struct alignas(16) ObsSegsLds {            /* 528 B of the 1 KiB the host plans keep for static LDS */
-  int64_t pre[C2D_EV_SHARDS + 1];
-  const double* base[C2D_EV_SHARDS];
-};
-
-/* before the kernel's first __syncthreads */
-__device__ __forceinline__ void obs_stage_segs(ObsSegsLds& L, const ObsSegs& S) {
-  if (threadIdx.x <= (unsigned)S.nseg) L.pre[threadIdx.x] = S.pre[threadIdx.x];
-  if (threadIdx.x < (unsigned)S.nseg) L.base[threadIdx.x] = S.base[threadIdx.x];
-}
-
-/* n doubles from global memory into LDS, by the whole workgroup; dst + n */
-__device__ __forceinline__ double* obs_stage(double* dst, const double* src, int n) {
-  for (int i = threadIdx.x; i < n; i += OBS_BLOCK) dst[i] = src[i];
-  return dst + n;
-}
-
-/* what every observer needs of an event, computed once */
-struct ObsEvent {
-  double t_bound, E, ew, z;
-  double mu_c;                             /* -wmu */
-  double rcos;                             /* r cos(phi) */
-};
-
-__device__ __forceinline__ ObsEvent obs_fetch(const ObsSegsLds& L, int nseg, int64_t ee) {
-  int sg = 0;                              /* last segment with pre[sg] <= ee */
-  for (int hi = nseg - 1; sg < hi;) {
-    const int m = (sg + hi + 1) >> 1;
-    if (L.pre[m] <= ee) sg = m; else hi = m - 1;
-  }
-  const double* v = L.base[sg] + (ee - L.pre[sg]) * C2D_EVENT_WORDS;
-  ObsEvent ev;
-  ev.t_bound = v[0]; ev.E = v[1]; ev.ew = v[2];
-  const double r = v[3];
-  ev.z = v[4];
-  ev.mu_c = -v[5];
-  ev.rcos = r * c2d_cos(v[6]);
-  return ev;
-}
-
-/* One histogram as a lane sees it: the single observer's (ObsDev) or a set
- * member's (ObsSetMember).  Edges and the privatised leading rows are in LDS;
- * bins h = row * n_mu * n_e + col with row = time bin, and h < nl lives in LDS. */
-struct ObsView {
-  double G, betta, rmax, t_offset;
-  int32_t mode, n_t, n_mu, n_e;
-  int32_t sorted_t, sorted_mu, sorted_e;
-  const double *t0, *t1, *mu0, *mu1, *E0, *E1;   /* LDS */
-  double *hF, *hF2, *hC;                         /* LDS: nl bins each */
-  int nl;
-  double *F, *F2, *cnt;                          /* global */
-};
-
-template <class D>
-__device__ __forceinline__ ObsView obs_view(const D& d, double betta, double* edges, double* hist) {
-  ObsView V;
-  V.G = d.gam_bulk; V.betta = betta; V.rmax = d.rmax; V.t_offset = d.t_offset;
-  V.mode = d.mode; V.n_t = d.n_t; V.n_mu = d.n_mu; V.n_e = d.n_e;
-  V.sorted_t = d.sorted_t; V.sorted_mu = d.sorted_mu; V.sorted_e = d.sorted_e;
-  V.t0 = edges; V.t1 = V.t0 + d.n_t;
-  V.mu0 = V.t1 + d.n_t; V.mu1 = V.mu0 + d.n_mu;
-  V.E0 = V.mu1 + d.n_mu; V.E1 = V.E0 + d.n_e;
-  V.nl = d.lds_rows * d.n_mu * d.n_e;
-  V.hF = hist; V.hF2 = V.hF + V.nl; V.hC = V.hF2 + V.nl;
-  V.F = d.F; V.F2 = d.F2; V.cnt = d.cnt;
-  return V;
-}
-
 /* LDS bins: plain per-lane LDS atomics; the rest: wave-aggregated global
  * atomics.  Every lane of the wave calls it (h = -1: nothing to add). */
 __device__ __forceinline__ void obs_add(const ObsView& V, int h, double w) {
@@ -168,39 +65,12 @@ __device__ __forceinline__ void obs_add(const ObsView& V, int h, double w) {
   agg_add(V.F, V.F2, V.cnt, h >= V.nl ? h : -1, w);
 }
 
-/* Boost, light-travel time, bin decision and add of one event in one
- * histogram.  Wave-uniform control flow down to agg_add: no early return for
- * an event past the end (!valid) or outside the window, they carry h = -1. */
+/* Boost, light-travel time, bin decision (c2d_obsbin.h) and add of one event
+ * in one histogram.  Wave-uniform control flow down to agg_add: no early
+ * return for an event past the end (!valid) or outside the window, they
+ * carry h = -1. */
 __device__ __forceinline__ void obs_bin_event(const ObsView& V, const ObsEvent& ev, bool valid) {
-  /* pspt.c:253-272 / plcm.c:390-399 */
-  const double G = V.G, betta = V.betta;
-  double mu = ev.mu_c;
-  const double doppler = G * (1. + mu * betta);
-  const double t_bound = (ev.t_bound - betta * ev.z * 3.33333333e-11) / doppler;
-  const double E = ev.E * doppler;
-  const double ew = ev.ew * doppler;
-  mu = (mu + betta) / (1. + mu * betta);
-  const double cdt = ev.z * mu / G + __builtin_sqrt(1. - mu * mu) * (V.rmax - ev.rcos);
-  double time = t_bound + 3.33333333e-11 * cdt;
-  if (V.mode == C2D_OBS_SED) {
-    int h = -1;
-    if (valid && !(mu < V.mu0[0] || mu > V.mu1[0])) {          /* pspt.c:274 */
-      const int k = first_bin(V.E0, V.E1, V.n_e, V.sorted_e, E);
-      const int m = first_bin(V.t0, V.t1, V.n_t, V.sorted_t, time);
-      if (k < V.n_e && m < V.n_t) h = m * V.n_e + k;
-    }
-    obs_add(V, h, ew);
-  } else {
-    time -= V.t_offset;                                        /* plcm.c:407-408 */
-    int row = -1;
-    if (valid && !(time < 0.)) {
-      const int k = first_bin(V.t0, V.t1, V.n_t, V.sorted_t, time);
-      const int m = first_bin(V.mu0, V.mu1, V.n_mu, V.sorted_mu, mu);
-      if (k < V.n_t && m < V.n_mu) row = (k * V.n_mu + m) * V.n_e;
-    }
-    for (int l = 0; l < V.n_e; l++)                            /* every band containing E */
-      obs_add(V, (row >= 0 && E >= V.E0[l] && E < V.E1[l]) ? row + l : -1, ew);
-  }
+  obs_decide(V, ev, valid, [&V](int h, double w) { obs_add(V, h, w); });
 }
 
 /* the workgroup's non-zero LDS bins to global memory (after a __syncthreads) */
@@ -280,20 +150,6 @@ __global__ void __launch_bounds__(OBS_BLOCK) c2d_obs_set_kernel(const ObsSetDev 
 }
 
 }  // namespace c2d
-
-/* the launch's non-empty segments, back to back; false when there is none */
-static bool obs_segs(c2d::ObsSegs& S, const double* const* ev, const int64_t* n, int nseg) {
-  int k = 0;
-  S.pre[0] = 0;
-  for (int s = 0; s < nseg; s++) {
-    if (n[s] <= 0) continue;
-    S.base[k] = ev[s];
-    S.pre[k + 1] = S.pre[k] + n[s];
-    k++;
-  }
-  S.nseg = k;
-  return k > 0;
-}
 
 /* one launch of the set kernel over nseg event segments; its dynamic LDS is
  * the plan's (edges + privatised rows) */

@@ -230,6 +230,24 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
     lib.c2d_obs_set_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), pi32]
     lib.c2d_obs_set_write.restype = C.c_int
     lib.c2d_obs_set_write.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int32, C.c_int32]
+    pu64 = C.POINTER(C.c_uint64)
+    lib.c2d_obs_set_exact.restype = C.c_int
+    lib.c2d_obs_set_exact.argtypes = [vp, C.c_double]
+    lib.c2d_obs_set_exact_info.restype = C.c_int
+    lib.c2d_obs_set_exact_info.argtypes = [vp, C.c_int32, pi32, C.POINTER(C.c_int64)]
+    lib.c2d_obs_set_state_words.restype = C.c_int
+    lib.c2d_obs_set_state_words.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+    lib.c2d_obs_set_state.restype = C.c_int
+    lib.c2d_obs_set_state.argtypes = [vp, C.c_int32, pu64, C.c_int64]
+    lib.c2d_obs_set_merge.restype = C.c_int
+    lib.c2d_obs_set_merge.argtypes = [vp, C.c_int32, pu64, C.c_int64]
+    lib.c2d_obs_exact_host.restype = C.c_int
+    lib.c2d_obs_exact_host.argtypes = [C.POINTER(abi.ObsBins), C.c_double, C.POINTER(C.c_double), C.c_int64, pu64,
+                                       C.c_int64]
+    lib.c2d_obs_state_merge.restype = C.c_int
+    lib.c2d_obs_state_merge.argtypes = [pu64, C.c_int64, pu64, C.c_int64]
+    lib.c2d_obs_state_result.restype = C.c_int
+    lib.c2d_obs_state_result.argtypes = [pu64, C.c_int64] + [C.POINTER(C.c_double)] * 3
     lib.c2d_electron_state.restype = C.c_int
     lib.c2d_electron_state.argtypes = [vp, abi.MArray3, abi.MArray3]
     lib.c2d_comm_unique_id.restype = C.c_int
@@ -984,6 +1002,34 @@ class Engine:
         the directory of plcm's files ("" = the deck's name / ".")."""
         self._check(self.lib.c2d_obs_set_write(self.ctx, int(member), str(path).encode(), int(factor),
                                                int(world_sum)))
+
+    def obs_set_exact(self, w_max: float) -> None:
+        """Make the observer set exact (c2d_obs_set_exact): integer sums, the
+        same bits for any event order, batch split or shard count.  w_max
+        bounds the rest-frame weight of any single event."""
+        self._check(self.lib.c2d_obs_set_exact(self.ctx, float(w_max)))
+
+    def obs_set_exact_info(self, member: int):
+        """(e, n_rejected) of a member of an exact set: its exponent bound
+        and the events whose weight the bound did not admit."""
+        e, r = C.c_int32(), C.c_int64()
+        self._check(self.lib.c2d_obs_set_exact_info(self.ctx, int(member), C.byref(e), C.byref(r)))
+        return e.value, r.value
+
+    def obs_set_state(self, member: int) -> np.ndarray:
+        """The integers of a member of an exact set as its state, u64 words
+        (include/compton2d.h "Exact observer sets")."""
+        n = C.c_int64()
+        self._check(self.lib.c2d_obs_set_state_words(self.ctx, int(member), C.byref(n)))
+        out = np.zeros(n.value, np.uint64)
+        self._check(self.lib.c2d_obs_set_state(self.ctx, int(member), out.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               out.size))
+        return out
+
+    def obs_set_merge(self, member: int, state) -> None:
+        """Add an exported state into a member of an exact set."""
+        s = np.ascontiguousarray(state, np.uint64).reshape(-1)
+        self._check(self.lib.c2d_obs_set_merge(self.ctx, int(member), s.ctypes.data_as(C.POINTER(C.c_uint64)), s.size))
 
     def fp_tridag(self, a, b, c, r, x0=None) -> np.ndarray:
         """Batched tridag (src/update2d.f:2476-2518); arrays [ncell, nt]."""

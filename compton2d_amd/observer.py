@@ -366,10 +366,15 @@ def bin_event_files(engine, binning: Binning, files: Iterable) -> Histogram:
     return Histogram(F, F2, cnt, ms)
 
 
-def bin_event_files_set(engine, binnings: Sequence[Binning], files: Iterable) -> List[Histogram]:
+def bin_event_files_set(engine, binnings: Sequence[Binning], files: Iterable,
+                        exact_w_max: Optional[float] = None) -> List[Histogram]:
     """Histogram event files into every binning of `binnings`, one pass over
-    each file (c2d_obs_set_accumulate_file)."""
+    each file (c2d_obs_set_accumulate_file).  exact_w_max: a bound on one
+    event's rest-frame weight; the sums are then exact integers, rounded
+    once, whatever the order of the files (c2d_obs_set_exact)."""
     engine.obs_set_clear()
+    if exact_w_max is not None:
+        engine.obs_set_exact(exact_w_max)
     ids = [engine.obs_set_add(b) for b in binnings]
     for f in files:
         engine.obs_set_accumulate_file(f)
@@ -377,18 +382,94 @@ def bin_event_files_set(engine, binnings: Sequence[Binning], files: Iterable) ->
     return [Histogram(*engine.obs_set_result(i), ms) for i in ids]
 
 
-def bin_events_set(engine, binnings: Sequence[Binning],
-                   events: Iterable[Optional[np.ndarray]]) -> List[Histogram]:
+def bin_events_set(engine, binnings: Sequence[Binning], events: Iterable[Optional[np.ndarray]],
+                   exact_w_max: Optional[float] = None) -> List[Histogram]:
     """Histogram event batches into every binning of `binnings` in one pass
     over each batch (the engine's observer set, c2d_obs_set_*; None = the
     device event buffer of the last transport step).  kernel_ms is the set's
-    device time, the same on every histogram."""
+    device time, the same on every histogram.  exact_w_max: as in
+    bin_event_files_set."""
     engine.obs_set_clear()
+    if exact_w_max is not None:
+        engine.obs_set_exact(exact_w_max)
     ids = [engine.obs_set_add(b) for b in binnings]
     for ev in events:
         engine.obs_set_accumulate(ev)
     ms, _ = engine.obs_set_kernel_ms()
     return [Histogram(*engine.obs_set_result(i), ms) for i in ids]
+
+
+# ---------------------------------------------------------------------------
+# exact sums: the state of a member on the host (c2d_obs_exact_host & co.)
+# ---------------------------------------------------------------------------
+STATE_HEAD_WORDS, STATE_BIN_WORDS = abi.OBS_STATE_HEAD_WORDS, abi.OBS_STATE_BIN_WORDS
+_PU64 = C.POINTER(C.c_uint64)
+
+
+def state_words(binning: Binning) -> int:
+    """Words of a member's exported state."""
+    return STATE_HEAD_WORDS + STATE_BIN_WORDS * binning.n_t * binning.n_mu * binning.n_e
+
+
+def state_info(state) -> dict:
+    """The head of a state: mode, shape, exponent bound e, binning digest,
+    n_rejected and payload digest."""
+    s = np.ascontiguousarray(state, np.uint64).reshape(-1)
+    w = [int(x) for x in s[:STATE_HEAD_WORDS]]
+    e = w[4] - (1 << 64) if w[4] >> 63 else w[4]
+    return {"magic": w[0], "version": w[1] & 0xFFFFFFFF, "mode": w[1] >> 32, "n_t": w[2] & 0xFFFFFFFF,
+            "n_mu": w[2] >> 32, "n_e": w[3] & 0xFFFFFFFF, "e": e, "bins_digest": w[5], "n_rejected": w[6],
+            "payload_digest": w[7]}
+
+
+def exact_host(binning: Binning, w_max: float, events, state=None) -> np.ndarray:
+    """The exact accumulation of `events` on the host (c2d_obs_exact_host, no
+    GPU): a new state, or `state` (of the same binning and w_max) with the
+    events added; the argument is not changed."""
+    from .engine import C2DError, load_library
+    lib = load_library()
+    ev = np.ascontiguousarray(events, np.float64).reshape(-1, abi.EVENT_WORDS)
+    out = np.zeros(state_words(binning), np.uint64) if state is None else \
+        np.array(state, np.uint64, copy=True).reshape(-1)
+    b = binning.to_ctypes()
+    rc = lib.c2d_obs_exact_host(C.byref(b), float(w_max), ev.ctypes.data_as(abi.PD), len(ev),
+                                out.ctypes.data_as(_PU64), out.size)
+    if rc != 0:
+        raise C2DError(rc, "c2d_obs_exact_host rejected its arguments")
+    return out
+
+
+def state_merge(into, other) -> np.ndarray:
+    """The sum of two states of one binning (c2d_obs_state_merge); neither
+    argument is changed."""
+    from .engine import C2DError, load_library
+    lib = load_library()
+    a = np.array(into, np.uint64, copy=True).reshape(-1)
+    b = np.ascontiguousarray(other, np.uint64).reshape(-1)
+    rc = lib.c2d_obs_state_merge(a.ctypes.data_as(_PU64), a.size, b.ctypes.data_as(_PU64), b.size)
+    if rc != 0:
+        raise C2DError(rc, "c2d_obs_state_merge refused the states")
+    return a
+
+
+def state_result(state) -> Histogram:
+    """A state's integers as doubles, rounded once per bin
+    (c2d_obs_state_result)."""
+    from .engine import C2DError, load_library
+    lib = load_library()
+    s = np.ascontiguousarray(state, np.uint64).reshape(-1)
+    if s.size < STATE_HEAD_WORDS:
+        raise C2DError(-1, "shorter than a state's head")
+    i = state_info(s)
+    shape = (i["n_t"], i["n_mu"], i["n_e"])
+    if s.size != STATE_HEAD_WORDS + STATE_BIN_WORDS * shape[0] * shape[1] * shape[2]:
+        raise C2DError(-1, "the word count is not what the head's shape says")
+    F, F2, cnt = (np.zeros(shape) for _ in range(3))
+    rc = lib.c2d_obs_state_result(s.ctypes.data_as(_PU64), s.size, F.ctypes.data_as(abi.PD),
+                                  F2.ctypes.data_as(abi.PD), cnt.ctypes.data_as(abi.PD))
+    if rc != 0:
+        raise C2DError(rc, "c2d_obs_state_result: not a state, or its payload digest fails")
+    return Histogram(F, F2, cnt)
 
 
 # ---------------------------------------------------------------------------

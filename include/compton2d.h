@@ -729,8 +729,13 @@ int  c2d_last_census_file_ms(c2d_ctx* ctx, double* io_ms, double* wait_ms, doubl
  * state: step number, zone scalars).  NOT in a checkpoint: the tallies,
  * escape events, reflection results and timers of the finished step (they
  * are outputs; after a restore they read as on a fresh context), and the
- * observer accumulations (c2d_obs_*, c2d_obs_set_*): they are sums, so a
- * host reads them before it saves and adds them afterwards.
+ * observer accumulations (c2d_obs_*, c2d_obs_set_*): they are sums.  An
+ * exact set's (c2d_obs_set_exact) travel in the user blob: the host exports
+ * each member's state (c2d_obs_set_state) before it saves and merges it into
+ * the re-created set afterwards (c2d_obs_set_merge), bit for bit, as
+ * CoupledRun.save(observer_set=True) does.  The f64 sums have no such call:
+ * a host that keeps them reads them before it saves and adds them to the
+ * later results itself.
  *
  * The file (little-endian, every part 8-byte aligned; the same state gives
  * the same bytes: no timestamps, no host names):
@@ -973,6 +978,82 @@ int  c2d_obs_set_kernel_ms(c2d_ctx* ctx, double* ms, int32_t* launches);
  * are summed over the context's communicator first (every rank calls, rank
  * 0 writes). */
 int  c2d_obs_set_write(c2d_ctx* ctx, int32_t id, const char* path, int32_t factor, int32_t world_sum);
+
+/* Exact observer sets: order-independent sums.  The f64 sums
+ * above are added with atomics in an unspecified order, so two runs over the
+ * same events agree to rounding only.  After c2d_obs_set_exact every member
+ * of the set accumulates integers instead, and integer addition commutes:
+ * the same events give the same bits in any order, batch split, shard count
+ * or, through the exported state, across processes and checkpoints.
+ *
+ * The arithmetic.  E(x) is the frexp exponent (x = f 2^E(x), 0.5 <= f < 1).
+ * w_max bounds the rest-frame weight ew of any single event.  A member with
+ * bulk factor G has the exponent bound e = E(w_max) + E(2 G): a boosted
+ * weight w = ew G (1 + mu beta), |mu| <= 1, lies below 2^e.  Each bin holds
+ *   F      unsigned 128-bit, in units of 2^qF,  qF  = e - 84
+ *   F2     unsigned 128-bit, in units of 2^qF2, qF2 = 2 e - 84
+ *   count  unsigned 64-bit
+ * and an event that the bin decision of the f64 set puts into bin h adds
+ * floor(w / 2^qF) to F[h], floor(fl(w w) / 2^qF2) to F2[h] and 1 to
+ * count[h], with w and fl(w w) the doubles the f64 set adds.  Both addends
+ * are below 2^84: a bin has 2^44 worst-case addends of headroom.  An event
+ * whose w is NaN, negative or >= 2^e is added nowhere; if a bin would have
+ * taken it, it is counted in the member's n_rejected (once per event).
+ * Truncation depends on the addend alone, so 0 <= sum(w) - F 2^qF <
+ * count 2^qF.  -469 <= e <= 489 keeps every quantum and every sum a normal
+ * double.  Reported F, F2 and count are the integers scaled and rounded to
+ * nearest, ties to even: one rounding per bin.  A generous w_max costs only
+ * spare low bits (84 bits below 2^e are kept); one set too low surfaces as
+ * n_rejected, never as a silent loss.
+ *
+ * The state of a member, u64 words (little-endian when stored):
+ *   0 magic "C2DOBSX\0"        1 version u32 (1), mode u32 (C2D_OBS_SED | C2D_OBS_LC)
+ *   2 n_t u32, n_mu u32        3 n_e u32, zero u32
+ *   4 e, i64                   5 digest_sum of the words G, rmax, t_offset and the
+ *                                edges t0 t1 mu0 mu1 E0 E1 (the checkpoint's rule)
+ *   6 n_rejected               7 digest_sum of the payload
+ *   then 5 words per bin in [n_t][n_mu][n_e] order: F_lo F_hi F2_lo F2_hi count */
+#define C2D_OBS_STATE_HEAD_WORDS 8
+#define C2D_OBS_STATE_BIN_WORDS  5
+/* Make the set exact: after c2d_obs_set_clear and before the first
+ * accumulate (later: C2D_E_STATE, as a second call is).  Every member, added
+ * before or after the call, accumulates exactly, by all three accumulate
+ * routes; c2d_obs_set_clear ends exact mode.  C2D_E_ARG for a w_max that is
+ * not finite and positive, and, here or at the add, for a member whose e
+ * falls outside [-469, 489]; the set is then as it was.  On an exact set
+ * c2d_obs_set_result and c2d_obs_set_write give the rounded doubles, and
+ * C2D_E_NONFINITE, naming the count and w_max, when n_rejected != 0;
+ * c2d_obs_set_write with world_sum sums the integers over the communicator
+ * (32-bit halves in u64 containers, carries normalised afterwards) and
+ * c2d_obs_set_shape reports the rows the exact kernel privatises (a bin is 5
+ * words of LDS, not 3). */
+int  c2d_obs_set_exact(c2d_ctx* ctx, double w_max);
+/* A member's exponent bound and rejected events (either may be NULL).
+ * C2D_E_STATE on a set that is not exact, here and below. */
+int  c2d_obs_set_exact_info(c2d_ctx* ctx, int32_t id, int32_t* e, int64_t* n_rejected);
+/* The member's state: its size in words, and the words (cap < size:
+ * C2D_E_ARG). */
+int  c2d_obs_set_state_words(c2d_ctx* ctx, int32_t id, int64_t* words);
+int  c2d_obs_set_state(c2d_ctx* ctx, int32_t id, uint64_t* out, int64_t cap);
+/* Add an exported state into member `id` (sums, counts and n_rejected), e.g.
+ * another rank's, or a saved one into a re-created set after a restore; from
+ * then on the set takes no further member.  C2D_E_ARG, leaving the member
+ * unchanged, for another shape, mode, e or binning digest, a failed payload
+ * digest, or a sum that would carry out of bit 127. */
+int  c2d_obs_set_merge(c2d_ctx* ctx, int32_t id, const uint64_t* in, int64_t words);
+/* The host twin of the exact kernel for one binning, no context and no GPU:
+ * adds n events into `state` (cap words >= 8 + 5 n_t n_mu n_e), which is
+ * either zeroed (state[0] == 0: a fresh state is begun) or a state of this
+ * binning and bound.  C2D_E_ARG (state unchanged) for a bad binning, w_max
+ * or e, a short buffer or a state of another binning. */
+int  c2d_obs_exact_host(const c2d_obs_bins* bins, double w_max, const double* events, int64_t n,
+                        uint64_t* state, int64_t cap);
+/* into += from on the host, with c2d_obs_set_merge's checks. */
+int  c2d_obs_state_merge(uint64_t* into, int64_t into_words, const uint64_t* from, int64_t from_words);
+/* A state's rounded doubles ([n_t][n_mu][n_e] each; any may be NULL);
+ * C2D_E_ARG for words that are no state or fail the payload digest.
+ * n_rejected is word 6 of the state: the caller's to look at. */
+int  c2d_obs_state_result(const uint64_t* state, int64_t words, double* F, double* F2, double* count);
 
 /* Copy the context's device electron state (C2D_DEV_ELECTRONS) into the
  * caller's f_nt / Pnt views (either may have NULL data), e.g. before

@@ -680,6 +680,75 @@ module compton2d
        integer(c_int32_t), value :: factor, world_sum
      end function c2d_obs_set_write
 
+     ! ---- exact observer sets: integer sums, the same bits in any order
+     !      (compton2d.h "Exact observer sets"); a state is u64 words,
+     !      integer(c_int64_t) here: 8 of head, then 5 per bin ----
+     integer(c_int) function c2d_obs_set_exact(ctx, w_max) bind(C, name='c2d_obs_set_exact')
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), value :: w_max               ! bound on one event's rest-frame weight
+     end function c2d_obs_set_exact
+
+     integer(c_int) function c2d_obs_set_exact_info(ctx, id, e, n_rejected) &
+          bind(C, name='c2d_obs_set_exact_info')
+       import :: c_int, c_ptr, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), value :: id
+       integer(c_int32_t), intent(out) :: e
+       integer(c_int64_t), intent(out) :: n_rejected
+     end function c2d_obs_set_exact_info
+
+     integer(c_int) function c2d_obs_set_state_words(ctx, id, words) bind(C, name='c2d_obs_set_state_words')
+       import :: c_int, c_ptr, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), value :: id
+       integer(c_int64_t), intent(out) :: words
+     end function c2d_obs_set_state_words
+
+     integer(c_int) function c2d_obs_set_state(ctx, id, out, cap) bind(C, name='c2d_obs_set_state')
+       import :: c_int, c_ptr, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), value :: id
+       integer(c_int64_t), intent(out) :: out(*)
+       integer(c_int64_t), value :: cap
+     end function c2d_obs_set_state
+
+     integer(c_int) function c2d_obs_set_merge(ctx, id, state, words) bind(C, name='c2d_obs_set_merge')
+       import :: c_int, c_ptr, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), value :: id
+       integer(c_int64_t), intent(in) :: state(*)
+       integer(c_int64_t), value :: words
+     end function c2d_obs_set_merge
+
+     ! the host twin (no context, no GPU): n events added into `state`
+     integer(c_int) function c2d_obs_exact_host(bins, w_max, events, n, state, cap) &
+          bind(C, name='c2d_obs_exact_host')
+       import :: c_int, c_ptr, c_double, c_int64_t, c2d_obs_bins
+       type(c2d_obs_bins), intent(in) :: bins
+       real(c_double), value :: w_max
+       type(c_ptr), value :: events                  ! [7, n] f64
+       integer(c_int64_t), value :: n
+       integer(c_int64_t), intent(inout) :: state(*)
+       integer(c_int64_t), value :: cap
+     end function c2d_obs_exact_host
+
+     integer(c_int) function c2d_obs_state_merge(into, into_words, from, from_words) &
+          bind(C, name='c2d_obs_state_merge')
+       import :: c_int, c_int64_t
+       integer(c_int64_t), intent(inout) :: into(*)
+       integer(c_int64_t), value :: into_words
+       integer(c_int64_t), intent(in) :: from(*)
+       integer(c_int64_t), value :: from_words
+     end function c2d_obs_state_merge
+
+     integer(c_int) function c2d_obs_state_result(state, words, F, F2, cnt) bind(C, name='c2d_obs_state_result')
+       import :: c_int, c_ptr, c_int64_t
+       integer(c_int64_t), intent(in) :: state(*)
+       integer(c_int64_t), value :: words
+       type(c_ptr), value :: F, F2, cnt            ! [n_e, n_mu, n_t] in Fortran order
+     end function c2d_obs_state_result
+
      ! ---- RCCL tally all-reduce (replaces xec_add / graphics_collect,
      !      src/xec2d.f:325-399, and cens_add_up / E_add_up,
      !      src/update2d.f:1929-2078): rank 0 makes the id, the host
