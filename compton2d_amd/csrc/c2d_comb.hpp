@@ -1,6 +1,6 @@
 /*
- * c2d_comb.hpp — the device side of the census comb (comb.hip) as capi.cpp
- * drives it: the counters of one call and the kernel's launcher.  The rule
+ * c2d_comb.hpp — the device side of the census comb (comb.hip) as
+ * popctl_api.cpp drives it: the counters of one call and the kernel's launcher.  The rule
  * itself is c2d_comb.h.
  */
 #ifndef C2D_COMB_HPP
@@ -10,7 +10,7 @@
 #include <stdint.h>
 
 #include "c2d_comb.h"
-#include "c2d_device.hpp"
+#include "c2d_popctl.hpp"
 
 namespace c2d {
 
@@ -24,14 +24,13 @@ struct CombCtl {
 
 }  // namespace c2d
 
-/* One pass over census records [0, n).  hist != NULL: hist[digit below the
+/* One pass over the census records of p.  hist != NULL: hist[digit below the
  * prefix] += 1 for every matching pool record (C2D_COMB_BINS u64, zeroed by
  * the caller).  hist == NULL: the matching c values go to vals[0, cap), in any
  * order; ctl->n_collect counts them all.  grid_cap > 0 caps the workgroups.
  * Device pointers throughout. */
-extern "C" int c2d_launch_census_comb(c2d::CensusSoA cs, const int32_t* clist, int64_t n, int nz, int nr, int ngroup,
-                                      const int32_t* group_of_sp, const double* norm, uint64_t salt, uint64_t prefix,
+extern "C" int c2d_launch_census_comb(const c2d::CensusPass& p, const double* norm, uint64_t salt, uint64_t prefix,
                                       int prefix_bits, unsigned long long* hist, double* vals, int64_t cap,
-                                      c2d::CombCtl* ctl, int n_cu, int grid_cap, hipStream_t s);
+                                      c2d::CombCtl* ctl, int grid_cap);
 
 #endif /* C2D_COMB_HPP */

@@ -1,7 +1,8 @@
 /*
  * c2d_ctx.hpp — the context behind the C ABI (include/compton2d.h) and the
  * helpers every host translation unit of the library shares: fail, HIPCHK,
- * dalloc.  Private to csrc/: capi.cpp and obs_api.cpp include it.
+ * dalloc.  Private to csrc/: capi.cpp, obs_api.cpp and popctl_api.cpp include
+ * it; what the latter two call of capi.cpp is declared at the end.
  */
 #ifndef C2D_CTX_HPP
 #define C2D_CTX_HPP
@@ -205,11 +206,11 @@ struct c2d_ctx {
   c2d_cens_file* cfile = nullptr;       /* the census file calls' staging buffers (censtext.hip) */
   c2d_cens_times cens_times = {};       /* of the last c2d_census_write* / c2d_census_read* */
   unsigned long long* cens_bad = nullptr;   /* c2d_census_read: the first record out of range */
-  hipEvent_t cens_ev[2] = {nullptr, nullptr};
+  hipEvent_t cens_ev[3] = {nullptr, nullptr, nullptr};   /* timing, made on first use (census_events) */
   c2d_ckpt_stage* ckpt = nullptr;           /* the checkpoint calls' staging buffers (ckpt.hip) */
   c2d_ckpt_times ckpt_times = {};           /* of the last c2d_checkpoint_write / _read */
-  /* census population control (roulette.hip): its control block, tables and
-   * statistics in one allocation */
+  /* census population control (popctl_api.cpp): a pass's control block and
+   * tables in one allocation, cut anew by every call */
   unsigned char* rl_buf = nullptr;
   size_t rl_bytes = 0;
   float last_stats_ms = 0.f;                /* device time of the last c2d_census_stats kernel */
@@ -306,5 +307,17 @@ inline hipError_t dalloc(T** p, size_t n) {
 /* c2d_evparse_file over `path` with the context's staging buffers; *n = the
  * records handed to `sink` (capi.cpp) */
 int events_parse(c2d_ctx* c, const char* path, c2d_evr_sink sink, void* user, int64_t* n);
+
+/* ---- the census as popctl_api.cpp's passes see it (capi.cpp) ---- */
+int ensure_tmp(c2d_ctx* c, int64_t want);              /* tmp_rec holds at least `want` packed records */
+const int32_t* cens_list(const c2d_ctx* c);            /* the chunk list on the device; NULL: not chunked */
+int census_fits(c2d_ctx* c, const char* who, int64_t n);             /* n more records fit, or ..._OVERFLOW */
+int census_chunks_extend(c2d_ctx* c, const char* who, int64_t n);    /* chunked: room for them behind the census */
+int census_lost_error(c2d_ctx* c, const char* who);    /* C2D_E_STATE: `who` read a census that is lost */
+/* the census is records [0, n) of what the buffer (chunked: the list's first chunks) holds */
+void census_set_count(c2d_ctx* c, int64_t n);
+/* the census was partly rewritten: none is held until an import or a truncation */
+void census_mark_lost(c2d_ctx* c);
+int census_events(c2d_ctx* c);                         /* every event of cens_ev exists */
 
 #endif /* C2D_CTX_HPP */

@@ -1,7 +1,7 @@
 /*
  * c2d_roulette.hpp — the device side of census population control
- * (roulette.hip) as capi.cpp drives it: the control block the kernels of one
- * c2d_census_roulette call share, and their launchers.  The rule itself is
+ * (roulette.hip) as popctl_api.cpp drives it: the control block the kernels of
+ * one c2d_census_roulette call share, and their launchers.  The rule itself is
  * c2d_roulette.h.
  */
 #ifndef C2D_ROULETTE_HPP
@@ -10,8 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "c2d_device.hpp"
-#include "c2d_roulette.h"
+#include "c2d_popctl.hpp"
 
 namespace c2d {
 
@@ -55,19 +54,16 @@ constexpr size_t RL_STATS_LDS_MAX = 64 * 1024;
 
 }  // namespace c2d
 
-/* count[cell][group] (+= records) and energy[cell][group] (+= ew) over census
- * records [0, n); both zeroed by the caller.  Device pointers throughout. */
-extern "C" int c2d_launch_census_stats(c2d::CensusSoA cs, const int32_t* clist, int64_t n, int nz, int nr, int ngroup,
-                                       const int32_t* group_of_sp, unsigned long long* count, double* energy,
-                                       int n_cu, hipStream_t s);
-/* One slice [first, first + m) of the roulette pass: decide and pack into
+/* count[cell][group] (+= records) and energy[cell][group] (+= ew) over the
+ * census records of p; both zeroed by the caller.  Device pointers throughout. */
+extern "C" int c2d_launch_census_stats(const c2d::CensusPass& p, unsigned long long* count, double* energy);
+/* One slice [first, first + m) of the roulette pass (p.n is not read): decide and pack into
  * `scratch` (four columns of `cap` 16-byte entries, RL_SHARDS regions of
  * rl_region(m) records in each: RL_SHARDS * rl_region(m) <= cap), unpack at
  * the cursor, advance it.  pack = 0 only decides and sums (nothing is written
  * but ctl's n_tested, e_before, e_after). */
-extern "C" int c2d_launch_roulette_slice(c2d::CensusSoA cs, const int32_t* clist, int64_t first, int64_t m, int nz,
-                                         int nr, int ngroup, const int32_t* group_of_sp, const double* w_min,
+extern "C" int c2d_launch_roulette_slice(const c2d::CensusPass& p, int64_t first, int64_t m, const double* w_min,
                                          uint64_t salt, uint64_t* scratch, int64_t cap, c2d::RouletteCtl* ctl,
-                                         int pack, int n_cu, hipStream_t s);
+                                         int pack);
 
 #endif /* C2D_ROULETTE_HPP */

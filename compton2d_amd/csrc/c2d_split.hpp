@@ -1,7 +1,7 @@
 /*
- * c2d_split.hpp — the device side of census splitting (split.hip) as capi.cpp
- * drives it: the control block the kernels of one c2d_census_split call
- * share, and their launchers.  The rule itself is c2d_split.h.
+ * c2d_split.hpp — the device side of census splitting (split.hip) as
+ * popctl_api.cpp drives it: the control block the kernels of one
+ * c2d_census_split call share, and their launchers.  The rule itself is c2d_split.h.
  */
 #ifndef C2D_SPLIT_HPP
 #define C2D_SPLIT_HPP
@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "c2d_device.hpp"
+#include "c2d_popctl.hpp"
 #include "c2d_split.h"
 
 namespace c2d {
@@ -31,22 +31,19 @@ inline int64_t sp_tiles(int64_t n) { return (n + SP_TILE - 1) / SP_TILE; }
 
 }  // namespace c2d
 
-/* Per tile of SP_TILE census records of [0, n) the number of copies its
+/* Per tile of SP_TILE census records of p the number of copies its
  * records ask for, sum (m - 1), into cnt[tile]; n_split, e_before and
  * e_after into ctl (zeroed by the caller).  Device pointers throughout. */
-extern "C" int c2d_launch_split_count(c2d::CensusSoA cs, const int32_t* clist, int64_t n, int nz, int nr, int ngroup,
-                                      const int32_t* group_of_sp, const double* w_max, int max_copies, uint32_t* cnt,
-                                      c2d::SplitCtl* ctl, int n_cu, hipStream_t s);
+extern "C" int c2d_launch_split_count(const c2d::CensusPass& p, const double* w_max, int max_copies, uint32_t* cnt,
+                                      c2d::SplitCtl* ctl);
 /* off[t] = cnt[0] + ... + cnt[t - 1] over ntiles tiles, ctl->n_extra their
  * sum: one workgroup, strips of `strip` tiles (1..SP_SCAN_STRIP). */
 extern "C" int c2d_launch_split_scan(const uint32_t* cnt, int64_t ntiles, int64_t strip, int64_t* off,
                                      c2d::SplitCtl* ctl, hipStream_t s);
-/* The split records of [0, n) take their new ew; copy i of the k-th split
+/* The split records of p's [0, n) take their new ew; copy i of the k-th split
  * record of tile t goes to census item n + off[t] + (its place in the tile),
  * below n_after: the chunk list reaches that far. */
-extern "C" int c2d_launch_split_expand(c2d::CensusSoA cs, const int32_t* clist, int64_t n, int64_t n_after, int nz,
-                                       int nr, int ngroup, const int32_t* group_of_sp, const double* w_max,
-                                       int max_copies, uint64_t salt, const uint32_t* cnt, const int64_t* off,
-                                       int n_cu, hipStream_t s);
+extern "C" int c2d_launch_split_expand(const c2d::CensusPass& p, int64_t n_after, const double* w_max, int max_copies,
+                                       uint64_t salt, const uint32_t* cnt, const int64_t* off);
 
 #endif /* C2D_SPLIT_HPP */

@@ -21,9 +21,6 @@
 #include "c2d_rng.h"
 #include "reflect_host.h"
 #include "c2d_censfmt.h"
-#include "c2d_comb.hpp"
-#include "c2d_roulette.hpp"
-#include "c2d_split.hpp"
 
 extern "C" int c2d_launch_transport_exact(const KParams* P, const GenArgs* A, int grid, size_t lds,
                                           int trk, int refl, hipStream_t s);
@@ -966,7 +963,7 @@ __global__ void __launch_bounds__(256) c2d_chunk_scatter(CensusSoA cs, const int
                tmp + (r - r0) * C2D_CENSUS_REC_WORDS);
 }
 
-static int ensure_tmp(c2d_ctx* c, int64_t want) {
+int ensure_tmp(c2d_ctx* c, int64_t want) {
   want = std::max<int64_t>(want, 1 << 16);
   if (c->tmp_cap >= want) return C2D_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1131,16 +1128,30 @@ extern "C" int c2d_run_step(c2d_ctx* c) {
                 "c2d_census_truncate first");
   c->g0_launched = false;
   const int rc = run_step_body(c);
-  if (rc && c->chunked && c->g0_launched) {
-    c->n_census = 0;
-    c->n_clist = 0;
-    c->census_lost = true;
-  }
+  if (rc && c->chunked && c->g0_launched) census_mark_lost(c);
   return rc;
 }
 
-static int census_lost(c2d_ctx* c, const char* who) {
+int census_lost_error(c2d_ctx* c, const char* who) {
   return fail(c, C2D_E_STATE, "%s: the census was lost by a failed in-place step", who);
+}
+
+/* the two ways the census's size is set (c2d_ctx.hpp): to n records, and to none with the lost mark */
+void census_set_count(c2d_ctx* c, int64_t n) {
+  c->n_census = n;
+  if (c->chunked) c->n_clist = (n + C2D_CCHUNK - 1) / C2D_CCHUNK;
+  c->census_lost = false;
+}
+
+void census_mark_lost(c2d_ctx* c) {
+  census_set_count(c, 0);
+  c->census_lost = true;
+}
+
+int census_events(c2d_ctx* c) {
+  for (hipEvent_t& e : c->cens_ev)
+    if (!e) HIPCHK(c, hipEventCreate(&e));
+  return C2D_OK;
 }
 
 static int run_step_body(c2d_ctx* c) {
@@ -1644,7 +1655,7 @@ __global__ void __launch_bounds__(256) c2d_census_check_kernel(const uint64_t* _
   }
 }
 
-static const int32_t* cens_list(const c2d_ctx* c) { return c->chunked ? c->clist[c->ccur] : nullptr; }
+const int32_t* cens_list(const c2d_ctx* c) { return c->chunked ? c->clist[c->ccur] : nullptr; }
 
 /* m census records first, first + stride, ... to the host, as the
  * reference's record (d6: rpre zpre wmu phi ew xnu; i5: jgpsp jgplc jgpmu
@@ -1692,7 +1703,7 @@ static int census_download(c2d_ctx* c, int64_t first, int64_t stride, int64_t m,
 extern "C" int c2d_census_export_range(c2d_ctx* c, int64_t first, int64_t stride, double* d6,
                                        int32_t* i5, uint64_t* keys, int64_t cap, int64_t* n) {
   if (!c || !n || first < 0 || stride < 1) return C2D_E_ARG;
-  if (c->census_lost) return census_lost(c, "c2d_census_export_range");
+  if (c->census_lost) return census_lost_error(c, "c2d_census_export_range");
   const int64_t avail = first < c->n_census ? (c->n_census - first + stride - 1) / stride : 0;
   *n = avail;
   const int64_t m = std::min(cap, avail);
@@ -1704,7 +1715,7 @@ extern "C" int c2d_census_export_range(c2d_ctx* c, int64_t first, int64_t stride
 extern "C" int c2d_census_export(c2d_ctx* c, double* d6, int32_t* i5, uint64_t* keys, int64_t cap,
                                  int64_t* n) {
   if (!c || !n) return C2D_E_ARG;
-  if (c->census_lost) return census_lost(c, "c2d_census_export");
+  if (c->census_lost) return census_lost_error(c, "c2d_census_export");
   *n = c->n_census;
   const int64_t m = std::min(cap, c->n_census);
   if (m <= 0) return C2D_OK;
@@ -1764,16 +1775,14 @@ extern "C" int c2d_census_import(c2d_ctx* c, const double* d6, const int32_t* i5
     std::vector<int32_t> ids(k);
     for (int64_t i = 0; i < k; i++) ids[i] = (int32_t)i;
     if (k) HIPCHK(c, hipMemcpy(c->clist[c->ccur], ids.data(), k * sizeof(int32_t), hipMemcpyHostToDevice));
-    c->n_clist = k;
   }
-  c->n_census = n;
-  c->census_lost = false;
+  census_set_count(c, n);
   return C2D_OK;
 }
 
 extern "C" int c2d_census_pack(c2d_ctx* c, int64_t first, int64_t n, uint64_t* d_rec) {
   if (!c || first < 0 || n < 0 || (n > 0 && !d_rec)) return C2D_E_ARG;
-  if (c->census_lost) return census_lost(c, "c2d_census_pack");
+  if (c->census_lost) return census_lost_error(c, "c2d_census_pack");
   if (first + n > c->n_census)
     return fail(c, C2D_E_ARG, "c2d_census_pack: records [%lld, %lld) beyond the census (%lld)",
                 (long long)first, (long long)(first + n), (long long)c->n_census);
@@ -1789,7 +1798,7 @@ extern "C" int c2d_census_pack(c2d_ctx* c, int64_t first, int64_t n, uint64_t* d
 
 /* the census holds n more records than it does: C2D_E_CENSUS_OVERFLOW with
  * nothing written otherwise */
-static int census_fits(c2d_ctx* c, const char* who, int64_t n) {
+int census_fits(c2d_ctx* c, const char* who, int64_t n) {
   if (c->n_census + n > c->cfg.census_capacity)
     return fail(c, C2D_E_CENSUS_OVERFLOW, "%s: %lld + %lld > capacity %lld", who, (long long)c->n_census,
                 (long long)n, (long long)c->cfg.census_capacity);
@@ -1799,7 +1808,7 @@ static int census_fits(c2d_ctx* c, const char* who, int64_t n) {
 /* room for n more records behind the census (chunked): the list's last chunk
  * fills up first, then free chunks join the list.  A failure leaves the
  * census as it was. */
-static int census_chunks_extend(c2d_ctx* c, const char* who, int64_t n) {
+int census_chunks_extend(c2d_ctx* c, const char* who, int64_t n) {
   if (!c->chunked) return C2D_OK;
   const int64_t k = (c->n_census + n + C2D_CCHUNK - 1) / C2D_CCHUNK - c->n_clist;
   if (k > 0) {
@@ -1818,7 +1827,7 @@ static int census_chunks_extend(c2d_ctx* c, const char* who, int64_t n) {
 
 extern "C" int c2d_census_append(c2d_ctx* c, const uint64_t* d_rec, int64_t n) {
   if (!c || n < 0 || (n > 0 && !d_rec)) return C2D_E_ARG;
-  if (c->census_lost) return census_lost(c, "c2d_census_append");
+  if (c->census_lost) return census_lost_error(c, "c2d_census_append");
   { const int rc = census_fits(c, "c2d_census_append", n); if (rc) return rc; }
   if (n == 0) return C2D_OK;
   HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -1846,457 +1855,7 @@ extern "C" int c2d_census_append(c2d_ctx* c, const uint64_t* d_rec, int64_t n) {
 
 extern "C" int c2d_census_truncate(c2d_ctx* c, int64_t n) {
   if (!c || n < 0 || n > c->n_census) return C2D_E_ARG;
-  c->census_lost = false;
-  c->n_census = n;
-  if (c->chunked) c->n_clist = (n + C2D_CCHUNK - 1) / C2D_CCHUNK;
-  return C2D_OK;
-}
-
-/* ---- census population control (c2d_roulette.h, roulette.hip) ---- */
-/* ngroup and every entry of group_of_sp in range, or C2D_E_ARG (c may be NULL: the host twin) */
-static int roulette_args(c2d_ctx* c, const char* who, const int32_t* group_of_sp, int32_t ngroup) {
-  if (ngroup < 1 || ngroup > C2D_ROULETTE_GROUPS_MAX)
-    return fail(c, C2D_E_ARG, "%s: ngroup %d outside 1..%d", who, (int)ngroup, C2D_ROULETTE_GROUPS_MAX);
-  for (int i = 0; i < C2D_ROULETTE_NSP; i++)
-    if (group_of_sp[i] < 0 || group_of_sp[i] >= ngroup)
-      return fail(c, C2D_E_ARG, "%s: group_of_sp[%d] = %d outside 0..%d", who, i, (int)group_of_sp[i],
-                  (int)ngroup - 1);
-  return C2D_OK;
-}
-
-struct RlBufs {
-  RouletteCtl* ctl;
-  int32_t* group;               /* [C2D_ROULETTE_NSP]       */
-  double* w_min;                /* [ncell * ngroup]         */
-  unsigned long long* count;    /* [ncell * ngroup] (stats) */
-  double* energy;               /* [ncell * ngroup] (stats) */
-};
-
-/* the context's population-control allocation holds at least `need` bytes */
-static int rl_reserve(c2d_ctx* c, size_t need) {
-  if (c->rl_bytes < need) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rl_buf) (void)hipFree(c->rl_buf);
-    c->rl_buf = nullptr;
-    c->rl_bytes = 0;
-    HIPCHK(c, dalloc(&c->rl_buf, need));
-    c->rl_bytes = need;
-  }
-  return C2D_OK;
-}
-
-/* that allocation cut for nbins (cell, group) pairs, the group table uploaded */
-static int roulette_bufs(c2d_ctx* c, const int32_t* group_of_sp, int64_t nbins, RlBufs* b) {
-  const size_t head = (sizeof(RouletteCtl) + 255) / 256 * 256, grp = 768,
-               need = head + grp + 3 * sizeof(double) * (size_t)nbins;
-  static_assert(sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "roulette buffer layout");
-  { const int rc = rl_reserve(c, need); if (rc) return rc; }
-  b->ctl = reinterpret_cast<RouletteCtl*>(c->rl_buf);
-  b->group = reinterpret_cast<int32_t*>(c->rl_buf + head);
-  b->w_min = reinterpret_cast<double*>(c->rl_buf + head + grp);
-  b->count = reinterpret_cast<unsigned long long*>(b->w_min + nbins);
-  b->energy = reinterpret_cast<double*>(b->count + nbins);
-  HIPCHK(c, hipMemcpyAsync(b->group, group_of_sp, sizeof(int32_t) * C2D_ROULETTE_NSP, hipMemcpyHostToDevice,
-                           c->stream));
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_stats(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, int64_t* count,
-                                double* energy) {
-  if (!c) return C2D_E_ARG;
-  if (!group_of_sp || !count || !energy) return fail(c, C2D_E_ARG, "c2d_census_stats: a null pointer");
-  { const int rc = roulette_args(c, "c2d_census_stats", group_of_sp, ngroup); if (rc) return rc; }
-  if (c->census_lost) return census_lost(c, "c2d_census_stats");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const int64_t nbins = (int64_t)c->ncell * ngroup;
-  RlBufs b;
-  { const int rc = roulette_bufs(c, group_of_sp, nbins, &b); if (rc) return rc; }
-  HIPCHK(c, hipMemsetAsync(b.count, 0, 2 * sizeof(double) * (size_t)nbins, c->stream));   /* count | energy */
-  if (!c->cens_ev[0]) HIPCHK(c, hipEventCreate(&c->cens_ev[0]));
-  if (!c->cens_ev[1]) HIPCHK(c, hipEventCreate(&c->cens_ev[1]));
-  HIPCHK(c, hipEventRecord(c->cens_ev[0], c->stream));
-  HIPCHK(c, (hipError_t)c2d_launch_census_stats(c->cens[c->cur].soa(), cens_list(c), c->n_census, c->nz, c->nr,
-                                                (int)ngroup, b.group, b.count, b.energy, c->n_cu, c->stream));
-  HIPCHK(c, hipEventRecord(c->cens_ev[1], c->stream));
-  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are copied as they are");
-  HIPCHK(c, hipMemcpyAsync(count, b.count, sizeof(int64_t) * (size_t)nbins, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(energy, b.energy, sizeof(double) * (size_t)nbins, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipEventElapsedTime(&c->last_stats_ms, c->cens_ev[0], c->cens_ev[1]));
-  return C2D_OK;
-}
-
-extern "C" int c2d_last_census_stats_ms(c2d_ctx* c, double* ms) {
-  if (!c || !ms) return C2D_E_ARG;
-  *ms = (double)c->last_stats_ms;
-  return C2D_OK;
-}
-
-/* the pass itself; *began = the census has been (or may have been) rewritten */
-static int roulette_body(c2d_ctx* c, const RlBufs& b, int32_t ngroup, bool any_floor, uint64_t salt,
-                         hipEvent_t e0, hipEvent_t e1, RouletteCtl* res, float* ms, bool* began) {
-  const int64_t n = c->n_census;
-  const CensusSoA cs = c->cens[c->cur].soa();
-  HIPCHK(c, hipMemsetAsync(b.ctl, 0, sizeof(RouletteCtl), c->stream));
-  int64_t S = n;
-  if (any_floor) {
-    /* the scratch: a slice's records and the slack of its RL_SHARDS regions */
-    const int rc = ensure_tmp(c, std::min<int64_t>(n, int64_t(1) << 22) + (int64_t)RL_SHARDS * RL_TILE);
-    if (rc) return rc;
-    S = rl_slice(c->tmp_cap);
-    /* test knob: short slices force many rounds on a small census */
-    if (const char* e = getenv("C2D_ROULETTE_SLICE")) S = std::max<int64_t>(1, std::min<int64_t>(S, atoll(e)));
-  }
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  *began = any_floor;
-  for (int64_t first = 0; first < n; first += S)
-    HIPCHK(c, (hipError_t)c2d_launch_roulette_slice(cs, cens_list(c), first, std::min(S, n - first), c->nz, c->nr,
-                                                    (int)ngroup, b.group, b.w_min, salt, c->tmp_rec, c->tmp_cap,
-                                                    b.ctl, any_floor ? 1 : 0, c->n_cu, c->stream));
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res, b.ctl, sizeof *res, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipEventElapsedTime(ms, e0, e1));
-  if (!any_floor) res->W = (unsigned long long)n;
-  if ((int64_t)res->W > n)
-    return fail(c, C2D_E_STATE, "c2d_census_roulette: %llu records written of %lld read", res->W, (long long)n);
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_roulette(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* w_min,
-                                   uint64_t salt, c2d_roulette_out* out) {
-  if (!c) return C2D_E_ARG;
-  if (!group_of_sp || !w_min || !out) return fail(c, C2D_E_ARG, "c2d_census_roulette: a null pointer");
-  { const int rc = roulette_args(c, "c2d_census_roulette", group_of_sp, ngroup); if (rc) return rc; }
-  if (c->census_lost) return census_lost(c, "c2d_census_roulette");
-  const c2d_roulette_out zero = {};
-  *out = zero;
-  out->n_before = out->n_after = c->n_census;
-  if (c->n_census == 0) return C2D_OK;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const int64_t nbins = (int64_t)c->ncell * ngroup;
-  /* no floor that can test a record: the census is only summed, and stays as it is, order included */
-  bool any_floor = false;
-  for (int64_t i = 0; i < nbins && !any_floor; i++) any_floor = w_min[i] > 0.0 && std::isfinite(w_min[i]);
-  RlBufs b;
-  { const int rc = roulette_bufs(c, group_of_sp, nbins, &b); if (rc) return rc; }
-  HIPCHK(c, hipMemcpyAsync(b.w_min, w_min, sizeof(double) * (size_t)nbins, hipMemcpyHostToDevice, c->stream));
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIPCHK(c, hipEventCreate(&ev[0]));
-  if (hipEventCreate(&ev[1]) != hipSuccess) {
-    (void)hipEventDestroy(ev[0]);
-    return fail(c, C2D_E_HIP, "c2d_census_roulette: hipEventCreate");
-  }
-  RouletteCtl res = {};
-  float ms = 0.f;
-  bool began = false;
-  const int rc = roulette_body(c, b, ngroup, any_floor, salt, ev[0], ev[1], &res, &ms, &began);
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  if (rc) {
-    if (began) {   /* partly rewritten: lost, as after a failed in-place step */
-      (void)hipStreamSynchronize(c->stream);
-      c->n_census = 0;
-      if (c->chunked) c->n_clist = 0;
-      c->census_lost = true;
-    }
-    return rc;
-  }
-  c->n_census = (int64_t)res.W;
-  if (c->chunked) c->n_clist = (c->n_census + C2D_CCHUNK - 1) / C2D_CCHUNK;   /* the rest is free again */
-  out->n_after = c->n_census;
-  out->n_tested = (int64_t)res.n_tested;
-  out->e_before = res.e_before;
-  out->e_after = res.e_after;
-  out->kernel_ms = (double)ms;
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_roulette_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n,
-                                        int32_t nz, int32_t nr, const int32_t* group_of_sp, int32_t ngroup,
-                                        const double* w_min, uint64_t salt, uint8_t* keep, double* ew_out) {
-  if (n < 0 || nz < 1 || nz > C2D_MAXZONE || nr < 1 || nr > C2D_MAXZONE || !group_of_sp || !w_min) return C2D_E_ARG;
-  if (n > 0 && (!d6 || !i5 || !keys || !keep || !ew_out)) return C2D_E_ARG;
-  if (roulette_args(nullptr, "c2d_census_roulette_host", group_of_sp, ngroup)) return C2D_E_ARG;
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t* q = i5 + 5 * i;
-    if (q[3] < 1 || q[3] > nz || q[4] < 1 || q[4] > nr || q[0] < 0 || q[0] > 255) return C2D_E_ARG;
-  }
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t* q = i5 + 5 * i;
-    const int g = group_of_sp[c2d_roulette_sp((uint32_t)q[0])];
-    const double w = w_min[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + g];
-    keep[i] = c2d_roulette_decide(d6[6 * i + 4], w, keys[i], salt, ew_out + i) != C2D_ROULETTE_REMOVED ? 1 : 0;
-  }
-  return C2D_OK;
-}
-
-/* ---- census splitting (c2d_split.h, split.hip) ---- */
-static int split_args(c2d_ctx* c, const char* who, const int32_t* group_of_sp, int32_t ngroup, int32_t max_copies) {
-  { const int rc = roulette_args(c, who, group_of_sp, ngroup); if (rc) return rc; }
-  if (max_copies < 2 || max_copies > C2D_SPLIT_COPIES_MAX)
-    return fail(c, C2D_E_ARG, "%s: max_copies %d outside 2..%d", who, (int)max_copies, C2D_SPLIT_COPIES_MAX);
-  return C2D_OK;
-}
-
-struct SpBufs {
-  SplitCtl* ctl;
-  int32_t* group;     /* [C2D_ROULETTE_NSP] */
-  double* w_max;      /* [ncell * ngroup]   */
-  int64_t* off;       /* [ntiles]           */
-  uint32_t* cnt;      /* [ntiles]           */
-};
-
-/* the pass itself; *began = the census has been (or may have been) rewritten */
-static int split_body(c2d_ctx* c, const SpBufs& b, int32_t ngroup, int32_t max_copies, uint64_t salt, bool dry,
-                      hipEvent_t e0, hipEvent_t e1, hipEvent_t e2, SplitCtl* res, float* ms, bool* began) {
-  const int64_t n = c->n_census, ntiles = sp_tiles(n);
-  const CensusSoA cs = c->cens[c->cur].soa();
-  int64_t strip = SP_SCAN_STRIP;
-  /* test knob: short strips give the scan several rounds on a small census */
-  if (const char* e = getenv("C2D_SPLIT_STRIP")) strip = std::max<int64_t>(1, std::min<int64_t>(strip, atoll(e)));
-  HIPCHK(c, hipMemsetAsync(b.ctl, 0, sizeof(SplitCtl), c->stream));
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  HIPCHK(c, (hipError_t)c2d_launch_split_count(cs, cens_list(c), n, c->nz, c->nr, (int)ngroup, b.group, b.w_max,
-                                               (int)max_copies, b.cnt, b.ctl, c->n_cu, c->stream));
-  HIPCHK(c, (hipError_t)c2d_launch_split_scan(b.cnt, ntiles, strip, b.off, b.ctl, c->stream));
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res, b.ctl, sizeof *res, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));   /* the only wait: the room to make depends on the total */
-  HIPCHK(c, hipEventElapsedTime(ms, e0, e1));
-  const int64_t extra = (int64_t)res->n_extra;
-  if (extra < (int64_t)res->n_split || extra > (int64_t)res->n_split * (C2D_SPLIT_COPIES_MAX - 1))
-    return fail(c, C2D_E_STATE, "c2d_census_split: %lld copies of %llu split records", (long long)extra, res->n_split);
-  if (dry || extra == 0) return C2D_OK;
-  { const int rc = census_fits(c, "c2d_census_split", extra); if (rc) return rc; }
-  { const int rc = census_chunks_extend(c, "c2d_census_split", extra); if (rc) return rc; }
-  *began = true;
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, (hipError_t)c2d_launch_split_expand(cs, cens_list(c), n, n + extra, c->nz, c->nr, (int)ngroup, b.group,
-                                                b.w_max, (int)max_copies, salt, b.cnt, b.off, c->n_cu, c->stream));
-  HIPCHK(c, hipEventRecord(e2, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms2 = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms2, e1, e2));
-  *ms += ms2;
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_split(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* w_max,
-                                int32_t max_copies, uint64_t salt, int32_t flags, c2d_split_out* out) {
-  if (!c) return C2D_E_ARG;
-  if (!group_of_sp || !w_max || !out) return fail(c, C2D_E_ARG, "c2d_census_split: a null pointer");
-  { const int rc = split_args(c, "c2d_census_split", group_of_sp, ngroup, max_copies); if (rc) return rc; }
-  if (flags & ~C2D_SPLIT_DRY) return fail(c, C2D_E_ARG, "c2d_census_split: unknown flag bits %#x", (unsigned)flags);
-  if (c->census_lost) return census_lost(c, "c2d_census_split");
-  const c2d_split_out zero = {};
-  *out = zero;
-  out->n_before = out->n_after = c->n_census;
-  if (c->n_census == 0) return C2D_OK;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const int64_t nbins = (int64_t)c->ncell * ngroup, ntiles = sp_tiles(c->n_census);
-  SpBufs b;
-  {
-    const size_t head = 256, grp = 768, tab = (sizeof(double) * (size_t)nbins + 255) / 256 * 256,
-                 offs = (sizeof(int64_t) * (size_t)ntiles + 255) / 256 * 256;
-    static_assert(sizeof(SplitCtl) <= 256 && sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "split buffer layout");
-    { const int rc = rl_reserve(c, head + grp + tab + offs + sizeof(uint32_t) * (size_t)ntiles); if (rc) return rc; }
-    b.ctl = reinterpret_cast<SplitCtl*>(c->rl_buf);
-    b.group = reinterpret_cast<int32_t*>(c->rl_buf + head);
-    b.w_max = reinterpret_cast<double*>(c->rl_buf + head + grp);
-    b.off = reinterpret_cast<int64_t*>(c->rl_buf + head + grp + tab);
-    b.cnt = reinterpret_cast<uint32_t*>(c->rl_buf + head + grp + tab + offs);
-  }
-  HIPCHK(c, hipMemcpyAsync(b.group, group_of_sp, sizeof(int32_t) * C2D_ROULETTE_NSP, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b.w_max, w_max, sizeof(double) * (size_t)nbins, hipMemcpyHostToDevice, c->stream));
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  for (int i = 0; i < 3; i++)
-    if (hipEventCreate(&ev[i]) != hipSuccess) {
-      for (int k = 0; k < i; k++) (void)hipEventDestroy(ev[k]);
-      return fail(c, C2D_E_HIP, "c2d_census_split: hipEventCreate");
-    }
-  SplitCtl res = {};
-  float ms = 0.f;
-  bool began = false;
-  const int rc = split_body(c, b, ngroup, max_copies, salt, (flags & C2D_SPLIT_DRY) != 0, ev[0], ev[1], ev[2], &res,
-                            &ms, &began);
-  for (int i = 0; i < 3; i++) (void)hipEventDestroy(ev[i]);
-  if (rc) {
-    if (began) {   /* partly rewritten: lost, as after a failed in-place step */
-      (void)hipStreamSynchronize(c->stream);
-      c->n_census = 0;
-      if (c->chunked) c->n_clist = 0;
-      c->census_lost = true;
-    }
-    return rc;
-  }
-  out->n_after = c->n_census + (int64_t)res.n_extra;
-  out->n_split = (int64_t)res.n_split;
-  out->e_before = res.e_before;
-  out->e_after = res.e_after;
-  out->kernel_ms = (double)ms;
-  if (!(flags & C2D_SPLIT_DRY)) c->n_census = out->n_after;
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_split_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n, int32_t nz,
-                                     int32_t nr, const int32_t* group_of_sp, int32_t ngroup, const double* w_max,
-                                     int32_t max_copies, uint64_t salt, int32_t* copies, double* ew_out) {
-  (void)salt;   /* the weights and the counts do not depend on it: the copies' keys do (c2d_split_key) */
-  if (n < 0 || nz < 1 || nz > C2D_MAXZONE || nr < 1 || nr > C2D_MAXZONE || !group_of_sp || !w_max) return C2D_E_ARG;
-  if (n > 0 && (!d6 || !i5 || !keys || !copies || !ew_out)) return C2D_E_ARG;
-  if (split_args(nullptr, "c2d_census_split_host", group_of_sp, ngroup, max_copies)) return C2D_E_ARG;
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t* q = i5 + 5 * i;
-    if (q[3] < 1 || q[3] > nz || q[4] < 1 || q[4] > nr || q[0] < 0 || q[0] > 255) return C2D_E_ARG;
-  }
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t* q = i5 + 5 * i;
-    const int g = group_of_sp[c2d_roulette_sp((uint32_t)q[0])];
-    const double W = w_max[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + g];
-    copies[i] = c2d_split_copies(d6[6 * i + 4], W, (int)max_copies, ew_out + i);
-  }
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_split_keys_host(const uint64_t* keys, const int32_t* copies, int64_t n, uint64_t salt,
-                                          uint64_t* keys_out) {
-  if (n < 0 || (n > 0 && (!keys || !copies || !keys_out))) return C2D_E_ARG;
-  for (int64_t i = 0; i < n; i++)
-    if (copies[i] < 1 || copies[i] > C2D_SPLIT_COPIES_MAX) return C2D_E_ARG;
-  int64_t o = 0;
-  for (int64_t i = 0; i < n; i++)
-    for (int k = 1; k < copies[i]; k++) keys_out[o++] = c2d_split_key(keys[i], salt, k);
-  return C2D_OK;
-}
-
-/* ---- the census comb (c2d_comb.h, comb.hip) ---- */
-/* what both device calls and the host twin judge before anything runs (c may be NULL: the host twin) */
-static int comb_args(c2d_ctx* c, const char* who, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
-                     int64_t ncell, uint64_t prefix, int32_t prefix_bits) {
-  { const int rc = roulette_args(c, who, group_of_sp, ngroup); if (rc) return rc; }
-  for (int64_t i = 0; i < ncell * ngroup; i++)
-    if (norm[i] > 0.0 && std::isfinite(norm[i]) && !c2d_comb_pow2(norm[i]))
-      return fail(c, C2D_E_ARG, "%s: norm[%lld] = %.17g is not a power of two", who, (long long)i, norm[i]);
-  if (!c2d_comb_prefix_ok(prefix, (int)prefix_bits))
-    return fail(c, C2D_E_ARG, "%s: prefix %#llx of %d bits (0, 11, 22, 33, 44 or 55 bits, none above them)", who,
-                (unsigned long long)prefix, (int)prefix_bits);
-  return C2D_OK;
-}
-
-struct CombBufs {
-  CombCtl* ctl;
-  int32_t* group;             /* [C2D_ROULETTE_NSP] */
-  unsigned long long* hist;   /* [C2D_COMB_BINS]    */
-  double* norm;               /* [ncell * ngroup]   */
-};
-
-/* one pass of comb.hip over the census: the tables uploaded, counters and histogram zeroed, the
- * kernel between the context's census events; vals == NULL: the histogram pass */
-static int comb_pass(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* norm, uint64_t salt,
-                     uint64_t prefix, int32_t prefix_bits, double* vals, int64_t cap, CombBufs* b) {
-  const int64_t nbins = (int64_t)c->ncell * ngroup;
-  static_assert(sizeof(CombCtl) <= 256 && sizeof(int32_t) * C2D_ROULETTE_NSP <= 768, "comb buffer layout");
-  const size_t hist_at = 256 + 768, norm_at = hist_at + sizeof(unsigned long long) * C2D_COMB_BINS;
-  { const int rc = rl_reserve(c, norm_at + sizeof(double) * (size_t)nbins); if (rc) return rc; }
-  b->ctl = reinterpret_cast<CombCtl*>(c->rl_buf);
-  b->group = reinterpret_cast<int32_t*>(c->rl_buf + 256);
-  b->hist = reinterpret_cast<unsigned long long*>(c->rl_buf + hist_at);
-  b->norm = reinterpret_cast<double*>(c->rl_buf + norm_at);
-  HIPCHK(c, hipMemsetAsync(c->rl_buf, 0, norm_at, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b->group, group_of_sp, sizeof(int32_t) * C2D_ROULETTE_NSP, hipMemcpyHostToDevice,
-                           c->stream));
-  HIPCHK(c, hipMemcpyAsync(b->norm, norm, sizeof(double) * (size_t)nbins, hipMemcpyHostToDevice, c->stream));
-  /* test knob: few workgroups make a small census run the tile loop */
-  int grid_cap = 0;
-  if (const char* e = getenv("C2D_COMB_GRID")) grid_cap = std::max(1, atoi(e));
-  if (!c->cens_ev[0]) HIPCHK(c, hipEventCreate(&c->cens_ev[0]));
-  if (!c->cens_ev[1]) HIPCHK(c, hipEventCreate(&c->cens_ev[1]));
-  HIPCHK(c, hipEventRecord(c->cens_ev[0], c->stream));
-  HIPCHK(c, (hipError_t)c2d_launch_census_comb(c->cens[c->cur].soa(), cens_list(c), c->n_census, c->nz, c->nr,
-                                               (int)ngroup, b->group, b->norm, salt, prefix, (int)prefix_bits,
-                                               vals ? nullptr : b->hist, vals, cap, b->ctl, c->n_cu, grid_cap,
-                                               c->stream));
-  HIPCHK(c, hipEventRecord(c->cens_ev[1], c->stream));
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_comb_hist(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
-                                    uint64_t salt, uint64_t prefix, int32_t prefix_bits, uint64_t* hist,
-                                    c2d_comb_out* out) {
-  if (!c) return C2D_E_ARG;
-  if (!group_of_sp || !norm || !hist || !out) return fail(c, C2D_E_ARG, "c2d_census_comb_hist: a null pointer");
-  { const int rc = comb_args(c, "c2d_census_comb_hist", group_of_sp, ngroup, norm, c->ncell, prefix, prefix_bits);
-    if (rc) return rc; }
-  if (c->census_lost) return census_lost(c, "c2d_census_comb_hist");
-  const c2d_comb_out zero = {};
-  *out = zero;
-  memset(hist, 0, sizeof(uint64_t) * C2D_COMB_BINS);
-  if (c->n_census == 0) return C2D_OK;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  CombBufs b;
-  { const int rc = comb_pass(c, group_of_sp, ngroup, norm, salt, prefix, prefix_bits, nullptr, 0, &b);
-    if (rc) return rc; }
-  CombCtl res = {};
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the histogram is copied as it is");
-  HIPCHK(c, hipMemcpyAsync(hist, b.hist, sizeof(uint64_t) * C2D_COMB_BINS, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&res, b.ctl, sizeof res, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->cens_ev[0], c->cens_ev[1]));
-  out->n_records = c->n_census;
-  out->n_fixed = (int64_t)res.n_fixed;
-  out->n_pool = c->n_census - (int64_t)res.n_fixed;
-  out->n_match = (int64_t)res.n_match;
-  out->kernel_ms = (double)ms;
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_comb_collect(c2d_ctx* c, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
-                                       uint64_t salt, uint64_t prefix, int32_t prefix_bits, double* crit_host,
-                                       int64_t cap, int64_t* n) {
-  if (!c) return C2D_E_ARG;
-  if (!group_of_sp || !norm || !n || cap < 0 || (cap > 0 && !crit_host))
-    return fail(c, C2D_E_ARG, "c2d_census_comb_collect: a null pointer or a negative cap");
-  { const int rc = comb_args(c, "c2d_census_comb_collect", group_of_sp, ngroup, norm, c->ncell, prefix, prefix_bits);
-    if (rc) return rc; }
-  if (c->census_lost) return census_lost(c, "c2d_census_comb_collect");
-  *n = 0;
-  if (c->n_census == 0) return C2D_OK;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  /* the values are staged in the packed-record scratch: C2D_CENSUS_REC_WORDS doubles a record of it */
-  const int64_t stage = std::min(cap, c->n_census);
-  { const int rc = ensure_tmp(c, (stage + C2D_CENSUS_REC_WORDS - 1) / C2D_CENSUS_REC_WORDS); if (rc) return rc; }
-  double* vals = reinterpret_cast<double*>(c->tmp_rec);
-  CombBufs b;
-  { const int rc = comb_pass(c, group_of_sp, ngroup, norm, salt, prefix, prefix_bits, vals, stage, &b);
-    if (rc) return rc; }
-  CombCtl res = {};
-  HIPCHK(c, hipMemcpyAsync(&res, b.ctl, sizeof res, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const int64_t got = std::min<int64_t>((int64_t)res.n_collect, stage);
-  if (got > 0) HIPCHK(c, hipMemcpy(crit_host, vals, sizeof(double) * (size_t)got, hipMemcpyDeviceToHost));
-  *n = (int64_t)res.n_collect;
-  return C2D_OK;
-}
-
-extern "C" int c2d_census_comb_host(const double* d6, const int32_t* i5, const uint64_t* keys, int64_t n, int32_t nz,
-                                    int32_t nr, const int32_t* group_of_sp, int32_t ngroup, const double* norm,
-                                    uint64_t salt, double* crit, uint8_t* fixed) {
-  if (n < 0 || nz < 1 || nz > C2D_MAXZONE || nr < 1 || nr > C2D_MAXZONE || !group_of_sp || !norm) return C2D_E_ARG;
-  if (n > 0 && (!d6 || !i5 || !keys || !crit || !fixed)) return C2D_E_ARG;
-  if (comb_args(nullptr, "c2d_census_comb_host", group_of_sp, ngroup, norm, (int64_t)nz * nr, 0, 0)) return C2D_E_ARG;
-  for (int64_t i = 0; i < n; i++)
-    if (i5[5 * i] < 0 || i5[5 * i] > 255) return C2D_E_ARG;
-  for (int64_t i = 0; i < n; i++) {
-    const int32_t* q = i5 + 5 * i;
-    const int on_grid = q[3] >= 1 && q[3] <= nz && q[4] >= 1 && q[4] <= nr;
-    double nm = 0.0;
-    if (on_grid) nm = norm[((int64_t)(q[3] - 1) * nr + (q[4] - 1)) * ngroup + group_of_sp[c2d_roulette_sp((uint32_t)q[0])]];
-    const double ew = d6[6 * i + 4];
-    fixed[i] = c2d_comb_fixed(ew, nm, on_grid) ? 1 : 0;
-    crit[i] = fixed[i] ? 0.0 : c2d_comb_critical(ew, nm, keys[i], salt);
-  }
+  census_set_count(c, n);
   return C2D_OK;
 }
 
@@ -3183,7 +2742,7 @@ static int census_write_source(void* user, int64_t first, int64_t n, double* d6,
 
 extern "C" int c2d_census_write(c2d_ctx* c, const char* path, int64_t* n_written) {
   if (!c || !path || !path[0]) return C2D_E_ARG;
-  if (c->census_lost) return census_lost(c, "c2d_census_write");
+  if (c->census_lost) return census_lost_error(c, "c2d_census_write");
   HIPCHK(c, hipSetDevice(c->cfg.device));
   char err[768] = "";
   const int rc = c2d_censtext_write(&c->cfile, c->cfg.device, c->stream, census_write_source, c, nullptr, nullptr,
@@ -3254,18 +2813,14 @@ static int census_store(c2d_ctx* c, CensStoreDst* d, const double* d6, const int
                         int64_t n) {
   if (!d->storing) {   /* the first records: the file's census replaces the context's */
     d->storing = true;
-    c->n_census = 0;
-    if (c->chunked) c->n_clist = 0;
-    c->census_lost = false;
+    census_set_count(c, 0);
   }
   if (c->n_census + n > c->cfg.census_capacity)
     return fail(c, C2D_E_CENSUS_OVERFLOW, "c2d_census_read: more than %lld records (census_capacity)",
                 (long long)c->cfg.census_capacity);
   { const int rc = ensure_tmp(c, n); if (rc) return rc; }
-  if (!c->cens_bad) {
-    HIPCHK(c, hipMalloc((void**)&c->cens_bad, sizeof(unsigned long long)));
-    for (hipEvent_t& e : c->cens_ev) HIPCHK(c, hipEventCreate(&e));
-  }
+  if (!c->cens_bad) HIPCHK(c, hipMalloc((void**)&c->cens_bad, sizeof(unsigned long long)));
+  { const int rc = census_events(c); if (rc) return rc; }
   unsigned long long bad = ~0ull;
   HIPCHK(c, hipMemsetAsync(c->cens_bad, 0xff, sizeof bad, c->stream));
   const int g = (int)std::min<int64_t>((n + 255) / 256, (int64_t)c->n_cu * 8);
@@ -3349,18 +2904,10 @@ extern "C" int c2d_census_read(c2d_ctx* c, const char* path, int64_t* n) {
   if (n) *n = rc ? 0 : got;
   if (rc) {
     rc = file_fail(c, rc, err);
-    if (d.storing) {   /* the previous census is gone and the file's is incomplete */
-      c->n_census = 0;
-      if (c->chunked) c->n_clist = 0;
-      c->census_lost = true;
-    }
+    if (d.storing) census_mark_lost(c);   /* the previous census is gone and the file's is incomplete */
     return rc;
   }
-  if (!d.storing) {    /* an empty file: an empty census */
-    c->n_census = 0;
-    if (c->chunked) c->n_clist = 0;
-    c->census_lost = false;
-  }
+  if (!d.storing) census_set_count(c, 0);   /* an empty file: an empty census */
   return C2D_OK;
 }
 
@@ -3404,7 +2951,7 @@ extern "C" int c2d_checkpoint_info(const char* path, c2d_ckpt_info* out) {
 extern "C" int c2d_checkpoint_write(c2d_ctx* c, const char* path, const void* user, int64_t user_bytes,
                                     int64_t* n_written) {
   if (!c || !path || !path[0] || user_bytes < 0 || (user_bytes > 0 && !user)) return C2D_E_ARG;
-  if (c->census_lost) return census_lost(c, "c2d_checkpoint_write");
+  if (c->census_lost) return census_lost_error(c, "c2d_checkpoint_write");
   HIPCHK(c, hipSetDevice(c->cfg.device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c2d_ckpt_header h;
@@ -3452,9 +2999,7 @@ static int ckpt_store_sink(void* user, const uint64_t* d_rec, int64_t n) {
   c2d_ctx* c = d->c;
   if (!d->append && !d->storing) {   /* the first records: the file's census replaces the context's */
     d->storing = true;
-    c->n_census = 0;
-    if (c->chunked) c->n_clist = 0;
-    c->census_lost = false;
+    census_set_count(c, 0);
   }
   return c2d_census_append(c, d_rec, n);
 }
@@ -3481,7 +3026,7 @@ extern "C" int c2d_checkpoint_read(c2d_ctx* c, const char* path, int64_t first, 
     return fail(c, C2D_E_ARG, "c2d_checkpoint_read: the azimuth encoding differs: '%s' holds %s, the context keeps %s "
                 "(comtot_mode)", path, h.encoded ? "cos(phi) and the switch bit" : "phi",
                 cens_encoded(c) ? "cos(phi) and the switch bit" : "phi");
-  if (append && c->census_lost) return census_lost(c, "c2d_checkpoint_read");
+  if (append && c->census_lost) return census_lost_error(c, "c2d_checkpoint_read");
   const int64_t lo = std::min(first, h.n_records);
   const int64_t hi = count < 0 ? h.n_records : std::min(h.n_records, lo + std::min(count, h.n_records));
   const int64_t n0 = append ? c->n_census : 0;
@@ -3513,21 +3058,11 @@ extern "C" int c2d_checkpoint_read(c2d_ctx* c, const char* path, int64_t first, 
   if (rc) {
     free_tabs();
     if (err[0]) rc = fail(c, rc, "%s", err);   /* else the sink's (c2d_census_append's) message stands */
-    if (append) {   /* back to what the census held */
-      c->n_census = n0;
-      if (c->chunked) c->n_clist = (n0 + C2D_CCHUNK - 1) / C2D_CCHUNK;
-    } else if (d.storing) {   /* the previous census is gone and the file's is incomplete */
-      c->n_census = 0;
-      if (c->chunked) c->n_clist = 0;
-      c->census_lost = true;
-    }
+    if (append) census_set_count(c, n0);         /* back to what the census held */
+    else if (d.storing) census_mark_lost(c);     /* the previous census is gone and the file's is incomplete */
     return rc;
   }
-  if (!append && !d.storing) {   /* no records: an empty census */
-    c->n_census = 0;
-    if (c->chunked) c->n_clist = 0;
-    c->census_lost = false;
-  }
+  if (!append && !d.storing) census_set_count(c, 0);   /* no records: an empty census */
   if (!census_only) {
     int i = 0;
     hipError_t e = hipSuccess;

@@ -137,20 +137,18 @@ c2d_census_comb_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int64_t 
 
 using namespace c2d;
 
-extern "C" int c2d_launch_census_comb(CensusSoA cs, const int32_t* clist, int64_t n, int nz, int nr, int ngroup,
-                                      const int32_t* group_of_sp, const double* norm, uint64_t salt, uint64_t prefix,
+extern "C" int c2d_launch_census_comb(const CensusPass& p, const double* norm, uint64_t salt, uint64_t prefix,
                                       int prefix_bits, unsigned long long* hist, double* vals, int64_t cap,
-                                      CombCtl* ctl, int n_cu, int grid_cap, hipStream_t s) {
-  if (n <= 0) return 0;
-  const int64_t tiles = (n + CB_TILE - 1) / CB_TILE;
-  int64_t grid = std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)std::max(n_cu, 1) * 8));
+                                      CombCtl* ctl, int grid_cap) {
+  if (p.n <= 0) return 0;
+  int64_t grid = census_grid(p.n, CB_TILE, p.n_cu, 8);
   if (grid_cap > 0) grid = std::min<int64_t>(grid, grid_cap);
-  grid = std::max<int64_t>(grid, (n >> 31) + 1);   /* a workgroup's u32 counts: n / grid + a tile < 2^32 records */
+  grid = std::max<int64_t>(grid, (p.n >> 31) + 1);   /* a workgroup's u32 counts: n / grid + a tile < 2^32 records */
   if (hist)
-    hipLaunchKernelGGL(c2d_census_comb_kernel<false>, dim3((unsigned)grid), dim3(CB_BLOCK), 0, s, cs, clist, n, nz, nr,
-                       ngroup, group_of_sp, norm, salt, prefix, prefix_bits, hist, vals, cap, ctl);
+    hipLaunchKernelGGL(c2d_census_comb_kernel<false>, dim3((unsigned)grid), dim3(CB_BLOCK), 0, p.stream, p.cs, p.clist,
+                       p.n, p.nz, p.nr, p.ngroup, p.group_of_sp, norm, salt, prefix, prefix_bits, hist, vals, cap, ctl);
   else
-    hipLaunchKernelGGL(c2d_census_comb_kernel<true>, dim3((unsigned)grid), dim3(CB_BLOCK), 0, s, cs, clist, n, nz, nr,
-                       ngroup, group_of_sp, norm, salt, prefix, prefix_bits, hist, vals, cap, ctl);
+    hipLaunchKernelGGL(c2d_census_comb_kernel<true>, dim3((unsigned)grid), dim3(CB_BLOCK), 0, p.stream, p.cs, p.clist,
+                       p.n, p.nz, p.nr, p.ngroup, p.group_of_sp, norm, salt, prefix, prefix_bits, hist, vals, cap, ctl);
   return (int)hipGetLastError();
 }

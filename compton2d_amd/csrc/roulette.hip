@@ -42,20 +42,6 @@ constexpr int RL_PER = 4;
 static_assert(RL_TILE == RL_BLOCK * RL_PER, "a tile is a workgroup's records");
 constexpr int RL_STATS_BLOCK_LDS = 1024;   /* threads of a stats workgroup with the histogram in LDS */
 
-/* group_of_sp into LDS, one byte an entry (groups < 32) */
-__device__ __forceinline__ void rl_load_groups(uint8_t* grp, const int32_t* __restrict__ group_of_sp) {
-  for (int i = (int)threadIdx.x; i < C2D_ROULETTE_NSP; i += (int)blockDim.x) grp[i] = (uint8_t)group_of_sp[i];
-  __syncthreads();
-}
-
-/* (cell, group) bin of a record, or -1 for a record whose cell is off the grid (never indexed with) */
-__device__ __forceinline__ int rl_bin(c2d_u4 tg, const uint8_t* grp, int nz, int nr, int ngroup) {
-  const int j = c2d_cens_j(tg.x), k = c2d_cens_k(tg.x);
-  if (j < 1 || j > nz || k < 1 || k > nr) return -1;
-  const int g = (int)grp[c2d_roulette_sp(tg.y)];
-  return ((j - 1) * nr + (k - 1)) * ngroup + (g < ngroup ? g : ngroup - 1);
-}
-
 template <bool LDS, int BLOCK>
 __global__ void __launch_bounds__(BLOCK)
 c2d_census_stats_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int64_t n, int nz, int nr, int ngroup,
@@ -71,7 +57,7 @@ c2d_census_stats_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int64_t
       cnt_l[b] = 0u;
       en_l[b] = 0.0;
     }
-  rl_load_groups(grp, group_of_sp);   /* ends in a barrier */
+  census_load_groups(grp, group_of_sp);   /* ends in a barrier */
   constexpr int64_t TILE = (int64_t)BLOCK * RL_PER;
   const int64_t ntiles = (n + TILE - 1) / TILE;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -91,7 +77,7 @@ c2d_census_stats_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int64_t
     for (int r = 0; r < RL_PER; r++) {
       const int64_t i = i0 + (int64_t)r * BLOCK;
       if (i >= n) continue;
-      const int b = rl_bin(tg[r], grp, nz, nr, ngroup);
+      const int b = census_bin(tg[r], grp, nz, nr, ngroup);
       if (b < 0) continue;
       if (LDS) {
         __hip_atomic_fetch_add(&cnt_l[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -128,7 +114,7 @@ c2d_roulette_decide_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int6
   __shared__ unsigned long long tile_base;
   __shared__ double red_e[2 * RL_WAVES];
   __shared__ unsigned long long red_n[RL_WAVES];
-  rl_load_groups(grp, group_of_sp);
+  census_load_groups(grp, group_of_sp);
   c2d_d2* s_rz = reinterpret_cast<c2d_d2*>(scratch);
   c2d_d2* s_wp = s_rz + cap;
   c2d_d2* s_ex = s_wp + cap;
@@ -158,7 +144,7 @@ c2d_roulette_decide_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int6
     for (int r = 0; r < RL_PER; r++) {
       keep[r] = false;
       if (slot[r] < 0) continue;
-      const int b = rl_bin(tg[r], grp, nz, nr, ngroup);
+      const int b = census_bin(tg[r], grp, nz, nr, ngroup);
       const double ew = ex[r].x;
       double ew_new = ew;
       int what = C2D_ROULETTE_UNTOUCHED;
@@ -293,47 +279,38 @@ __global__ void __launch_bounds__(RL_SHARDS) c2d_roulette_advance_kernel(Roulett
 
 using namespace c2d;
 
-namespace {
-unsigned rl_grid(int64_t records, int64_t tile, int n_cu, int per_cu) {
-  const int64_t tiles = (records + tile - 1) / tile;
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)std::max(n_cu, 1) * per_cu));
-}
-}  // namespace
-
-extern "C" int c2d_launch_census_stats(CensusSoA cs, const int32_t* clist, int64_t n, int nz, int nr, int ngroup,
-                                       const int32_t* group_of_sp, unsigned long long* count, double* energy,
-                                       int n_cu, hipStream_t s) {
-  if (n <= 0) return 0;
-  const size_t lds = (size_t)nz * nr * ngroup * (sizeof(double) + sizeof(uint32_t));
+extern "C" int c2d_launch_census_stats(const CensusPass& p, unsigned long long* count, double* energy) {
+  if (p.n <= 0) return 0;
+  const size_t lds = (size_t)p.nz * p.nr * p.ngroup * (sizeof(double) + sizeof(uint32_t));
   if (lds <= RL_STATS_LDS_MAX) {
     /* two resident workgroups a CU; each sees n / grid + a tile < 2^32 records */
-    const unsigned grid = std::max(rl_grid(n, (int64_t)RL_STATS_BLOCK_LDS * RL_PER, n_cu, 2),
-                                   (unsigned)(n >> 31) + 1u);
+    const unsigned grid = std::max(census_grid(p.n, (int64_t)RL_STATS_BLOCK_LDS * RL_PER, p.n_cu, 2),
+                                   (unsigned)(p.n >> 31) + 1u);
     hipLaunchKernelGGL((c2d_census_stats_kernel<true, RL_STATS_BLOCK_LDS>), dim3(grid), dim3(RL_STATS_BLOCK_LDS), lds,
-                       s, cs, clist, n, nz, nr, ngroup, group_of_sp, count, energy);
+                       p.stream, p.cs, p.clist, p.n, p.nz, p.nr, p.ngroup, p.group_of_sp, count, energy);
   } else {
-    hipLaunchKernelGGL((c2d_census_stats_kernel<false, RL_BLOCK>), dim3(rl_grid(n, RL_TILE, n_cu, 8)), dim3(RL_BLOCK),
-                       0, s, cs, clist, n, nz, nr, ngroup, group_of_sp, count, energy);
+    hipLaunchKernelGGL((c2d_census_stats_kernel<false, RL_BLOCK>), dim3(census_grid(p.n, RL_TILE, p.n_cu, 8)),
+                       dim3(RL_BLOCK), 0, p.stream, p.cs, p.clist, p.n, p.nz, p.nr, p.ngroup, p.group_of_sp, count,
+                       energy);
   }
   return (int)hipGetLastError();
 }
 
-extern "C" int c2d_launch_roulette_slice(CensusSoA cs, const int32_t* clist, int64_t first, int64_t m, int nz, int nr,
-                                         int ngroup, const int32_t* group_of_sp, const double* w_min, uint64_t salt,
-                                         uint64_t* scratch, int64_t cap, RouletteCtl* ctl, int pack, int n_cu,
-                                         hipStream_t s) {
+extern "C" int c2d_launch_roulette_slice(const CensusPass& p, int64_t first, int64_t m, const double* w_min,
+                                         uint64_t salt, uint64_t* scratch, int64_t cap, RouletteCtl* ctl, int pack) {
   if (m <= 0) return 0;
-  const unsigned grid = rl_grid(m, RL_TILE, n_cu, 8);
+  const unsigned grid = census_grid(m, RL_TILE, p.n_cu, 8);
+  const hipStream_t s = p.stream;
   if (!pack) {
-    hipLaunchKernelGGL(c2d_roulette_decide_kernel<false>, dim3(grid), dim3(RL_BLOCK), 0, s, cs, clist, first, m, nz, nr,
-                       ngroup, group_of_sp, w_min, salt, scratch, cap, (int64_t)0, ctl);
+    hipLaunchKernelGGL(c2d_roulette_decide_kernel<false>, dim3(grid), dim3(RL_BLOCK), 0, s, p.cs, p.clist, first, m,
+                       p.nz, p.nr, p.ngroup, p.group_of_sp, w_min, salt, scratch, cap, (int64_t)0, ctl);
     return (int)hipGetLastError();
   }
   const int64_t region = rl_region(m);
   if ((int64_t)RL_SHARDS * region > cap) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(c2d_roulette_decide_kernel<true>, dim3(grid), dim3(RL_BLOCK), 0, s, cs, clist, first, m, nz, nr,
-                     ngroup, group_of_sp, w_min, salt, scratch, cap, region, ctl);
-  hipLaunchKernelGGL(c2d_roulette_unpack_kernel, dim3(grid), dim3(RL_BLOCK), 0, s, cs, clist, scratch, cap, region,
+  hipLaunchKernelGGL(c2d_roulette_decide_kernel<true>, dim3(grid), dim3(RL_BLOCK), 0, s, p.cs, p.clist, first, m, p.nz,
+                     p.nr, p.ngroup, p.group_of_sp, w_min, salt, scratch, cap, region, ctl);
+  hipLaunchKernelGGL(c2d_roulette_unpack_kernel, dim3(grid), dim3(RL_BLOCK), 0, s, p.cs, p.clist, scratch, cap, region,
                      first + m, ctl);
   hipLaunchKernelGGL(c2d_roulette_advance_kernel, dim3(1), dim3(RL_SHARDS), 0, s, ctl, region);
   return (int)hipGetLastError();

@@ -44,24 +44,10 @@ constexpr int SP_PER = 4;
 static_assert(SP_TILE == SP_BLOCK * SP_PER, "a tile is a workgroup's records");
 static_assert(C2D_SPLIT_COPIES_MAX * SP_TILE < (1ll << 32), "a tile's extras fit a u32");
 
-/* group_of_sp into LDS, one byte an entry (groups < 32) */
-__device__ __forceinline__ void sp_load_groups(uint8_t* grp, const int32_t* __restrict__ group_of_sp) {
-  for (int i = (int)threadIdx.x; i < C2D_ROULETTE_NSP; i += (int)blockDim.x) grp[i] = (uint8_t)group_of_sp[i];
-  __syncthreads();
-}
-
-/* (cell, group) bin of a record, or -1 for a record whose cell is off the grid (never indexed with) */
-__device__ __forceinline__ int sp_bin(c2d_u4 tg, const uint8_t* grp, int nz, int nr, int ngroup) {
-  const int j = c2d_cens_j(tg.x), k = c2d_cens_k(tg.x);
-  if (j < 1 || j > nz || k < 1 || k > nr) return -1;
-  const int g = (int)grp[c2d_roulette_sp(tg.y)];
-  return ((j - 1) * nr + (k - 1)) * ngroup + (g < ngroup ? g : ngroup - 1);
-}
-
 /* m of a record and the weight of each of its m copies */
 __device__ __forceinline__ int sp_copies(c2d_d2 ex, c2d_u4 tg, const uint8_t* grp, int nz, int nr, int ngroup,
                                          const double* __restrict__ w_max, int max_copies, double* ew_new) {
-  const int b = sp_bin(tg, grp, nz, nr, ngroup);
+  const int b = census_bin(tg, grp, nz, nr, ngroup);
   *ew_new = ex.x;
   return b >= 0 ? c2d_split_copies(ex.x, w_max[b], max_copies, ew_new) : 1;
 }
@@ -74,7 +60,7 @@ c2d_split_count_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int64_t 
   __shared__ uint32_t wext[SP_WAVES];
   __shared__ double red_e[2 * SP_WAVES];
   __shared__ unsigned long long red_n[SP_WAVES];
-  sp_load_groups(grp, group_of_sp);
+  census_load_groups(grp, group_of_sp);
   const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
   double e_b = 0.0, e_a = 0.0;
   unsigned long long n_s = 0ull;
@@ -201,7 +187,7 @@ c2d_split_expand_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int64_t
   __shared__ uint32_t pre[SP_TILE];   /* copies asked for by the tile's records before this one */
   __shared__ c2d_d2 l_ex[SP_TILE];    /* the records' ex (ew already the copies') and tg words */
   __shared__ c2d_u4 l_tg[SP_TILE];
-  sp_load_groups(grp, group_of_sp);
+  census_load_groups(grp, group_of_sp);
   const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
   const int64_t ntiles = (n + SP_TILE - 1) / SP_TILE;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {   /* the same trips for every thread of the workgroup */
@@ -287,19 +273,11 @@ c2d_split_expand_kernel(CensusSoA cs, const int32_t* __restrict__ clist, int64_t
 
 using namespace c2d;
 
-namespace {
-unsigned sp_grid(int64_t records, int n_cu, int per_cu) {
-  const int64_t tiles = (records + SP_TILE - 1) / SP_TILE;
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)std::max(n_cu, 1) * per_cu));
-}
-}  // namespace
-
-extern "C" int c2d_launch_split_count(CensusSoA cs, const int32_t* clist, int64_t n, int nz, int nr, int ngroup,
-                                      const int32_t* group_of_sp, const double* w_max, int max_copies, uint32_t* cnt,
-                                      SplitCtl* ctl, int n_cu, hipStream_t s) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(c2d_split_count_kernel, dim3(sp_grid(n, n_cu, 8)), dim3(SP_BLOCK), 0, s, cs, clist, n, nz, nr,
-                     ngroup, group_of_sp, w_max, max_copies, cnt, ctl);
+extern "C" int c2d_launch_split_count(const CensusPass& p, const double* w_max, int max_copies, uint32_t* cnt,
+                                      SplitCtl* ctl) {
+  if (p.n <= 0) return 0;
+  hipLaunchKernelGGL(c2d_split_count_kernel, dim3(census_grid(p.n, SP_TILE, p.n_cu, 8)), dim3(SP_BLOCK), 0, p.stream,
+                     p.cs, p.clist, p.n, p.nz, p.nr, p.ngroup, p.group_of_sp, w_max, max_copies, cnt, ctl);
   return (int)hipGetLastError();
 }
 
@@ -311,13 +289,12 @@ extern "C" int c2d_launch_split_scan(const uint32_t* cnt, int64_t ntiles, int64_
   return (int)hipGetLastError();
 }
 
-extern "C" int c2d_launch_split_expand(CensusSoA cs, const int32_t* clist, int64_t n, int64_t n_after, int nz, int nr,
-                                       int ngroup, const int32_t* group_of_sp, const double* w_max, int max_copies,
-                                       uint64_t salt, const uint32_t* cnt, const int64_t* off, int n_cu,
-                                       hipStream_t s) {
-  if (n <= 0 || n_after <= n) return 0;
+extern "C" int c2d_launch_split_expand(const CensusPass& p, int64_t n_after, const double* w_max, int max_copies,
+                                       uint64_t salt, const uint32_t* cnt, const int64_t* off) {
+  if (p.n <= 0 || n_after <= p.n) return 0;
   /* 36 KB of LDS a workgroup: four of them, 16 waves, a CU */
-  hipLaunchKernelGGL(c2d_split_expand_kernel, dim3(sp_grid(n, n_cu, 4)), dim3(SP_BLOCK), 0, s, cs, clist, n, n_after,
-                     nz, nr, ngroup, group_of_sp, w_max, max_copies, salt, cnt, off);
+  hipLaunchKernelGGL(c2d_split_expand_kernel, dim3(census_grid(p.n, SP_TILE, p.n_cu, 4)), dim3(SP_BLOCK), 0, p.stream,
+                     p.cs, p.clist, p.n, n_after, p.nz, p.nr, p.ngroup, p.group_of_sp, w_max, max_copies, salt, cnt,
+                     off);
   return (int)hipGetLastError();
 }

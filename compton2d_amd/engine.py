@@ -467,6 +467,13 @@ class Engine:
             raise ValueError("group_of_sp holds %d entries, %d expected" % (g.size, abi.ROULETTE_NSP))
         return g
 
+    def _bin_table(self, table, ngroup: int, name: str, what: str) -> np.ndarray:
+        """`table` as contiguous f64 of nz * nr * ngroup entries, or ValueError naming it."""
+        t = np.ascontiguousarray(table, np.float64)
+        if t.size != self.nz * self.nr * int(ngroup) and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX:
+            raise ValueError("%s holds %d %s, %d expected" % (name, t.size, what, self.nz * self.nr * int(ngroup)))
+        return t
+
     def census_stats(self, group_of_sp, ngroup: int):
         """(count int64, energy f64), each [nz, nr, ngroup]: the census's
         records and their summed ew per cell and spectral group
@@ -489,11 +496,7 @@ class Engine:
         [nz, nr, ngroup] (c2d_census_roulette; the rule: popcontrol.roulette_numpy).
         Returns n_before, n_after, n_tested, e_before, e_after, kernel_ms."""
         g = self._group_table(group_of_sp)
-        w = None
-        if w_min is not None:
-            w = np.ascontiguousarray(w_min, np.float64)
-            if w.size != self.nz * self.nr * int(ngroup) and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX:
-                raise ValueError("w_min holds %d floors, %d expected" % (w.size, self.nz * self.nr * int(ngroup)))
+        w = None if w_min is None else self._bin_table(w_min, ngroup, "w_min", "floors")
         out = abi.RouletteOut()
         self._check(self.lib.c2d_census_roulette(self.ctx, g.ctypes.data, int(ngroup),
                                                  w.ctypes.data if w is not None else None,
@@ -508,11 +511,7 @@ class Engine:
         as it is.  Returns n_before, n_after, n_split, e_before, e_after,
         kernel_ms."""
         g = self._group_table(group_of_sp)
-        w = None
-        if w_max is not None:
-            w = np.ascontiguousarray(w_max, np.float64)
-            if w.size != self.nz * self.nr * int(ngroup) and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX:
-                raise ValueError("w_max holds %d ceilings, %d expected" % (w.size, self.nz * self.nr * int(ngroup)))
+        w = None if w_max is None else self._bin_table(w_max, ngroup, "w_max", "ceilings")
         out = abi.SplitOut()
         self._check(self.lib.c2d_census_split(self.ctx, g.ctypes.data, int(ngroup),
                                               w.ctypes.data if w is not None else None, int(max_copies),
@@ -521,11 +520,7 @@ class Engine:
         return {k: getattr(out, k) for k, _ in abi.SplitOut._fields_}
 
     def _comb_tables(self, group_of_sp, ngroup: int, norm):
-        g = self._group_table(group_of_sp)
-        nm = np.ascontiguousarray(norm, np.float64)
-        if nm.size != self.nz * self.nr * int(ngroup) and 1 <= int(ngroup) <= abi.ROULETTE_GROUPS_MAX:
-            raise ValueError("norm holds %d entries, %d expected" % (nm.size, self.nz * self.nr * int(ngroup)))
-        return g, nm
+        return self._group_table(group_of_sp), self._bin_table(norm, ngroup, "norm", "entries")
 
     def census_comb_hist(self, group_of_sp, ngroup: int, norm, salt: int, prefix: int = 0, prefix_bits: int = 0):
         """(hist int64 [2048], out dict): the digit histogram of the pool

@@ -377,6 +377,74 @@ def test_roulette_then_split_with_one_salt(eng, pool):
     same_census(by_key(*eng.census()), by_key(*want))                      # the roulette's order is free
 
 
+def check_stats(e, g, ng):
+    """c2d_census_stats of the census e holds against numpy's bincount of its records."""
+    d6, i5, _ = e.census()
+    b = ((i5[:, 3].astype(np.int64) - 1) * NR + (i5[:, 4] - 1)) * ng + g[np.minimum(i5[:, 0], abi.NPHOMAX)]
+    count, energy = e.census_stats(g, ng)
+    np.testing.assert_array_equal(count.reshape(-1), np.bincount(b, minlength=NZ * NR * ng))
+    np.testing.assert_allclose(energy.reshape(-1), np.bincount(b, weights=d6[:, 4], minlength=NZ * NR * ng),
+                               rtol=sum_tol(len(b)), atol=0.0)
+
+
+def check_comb(e, g, ng, norm, salt, collect):
+    """The comb's histogram of the census e holds (and, collect, its values) against the yardstick."""
+    crit, fixed = PC.comb_critical(*e.census(), NZ, NR, g, ng, norm, salt)
+    hist, out = e.census_comb_hist(g, ng, norm, salt)
+    want, counts = PC.comb_hist_numpy(crit, fixed)
+    np.testing.assert_array_equal(hist, want)
+    assert [out["n_records"], out["n_fixed"], out["n_pool"], out["n_match"]] == counts.tolist()
+    assert out["n_pool"] > 0
+    if collect:
+        p = crit[~fixed]
+        p = p[PC.comb_match(p, 0, 0)]
+        vals, cnt = e.census_comb_collect(g, ng, norm, salt, 0, 0, len(p))
+        assert cnt == len(p) == len(vals)
+        np.testing.assert_array_equal(np.sort(vals.view(np.uint64)), np.sort(p.view(np.uint64)))
+
+
+@pytest.mark.parametrize("inplace", [0, 1])
+def test_one_context_through_every_pass(pool, inplace):
+    """Stats, comb, roulette, split, stats and comb again in one context, ngroup 1 and 32 in turn:
+    every call cuts the context's scratch allocation anew, for tables of another size and in another
+    order each time.  On this 3 x 3 grid the allocation grows once, at the comb's first call (16 KB
+    of histogram; the stats call before it needs 10 KB), and is only re-cut afterwards: the split's
+    tile tables, seven tiles once 1025 records have grown past 5 * 1024, are a 256-byte piece each.
+    Each result against its yardstick, as the tests of the single passes hold it."""
+    d6, i5, keys, g, w = pool
+    n, salt = 1025, 41                                                     # two tiles, the second of one record
+    g1 = SC.group_table(1)
+    real = np.isfinite(w) & (w > 0)
+    pow2 = np.where(real, PC.pow2_ceil(np.where(real, w, 1.0)), 0.0)
+    with Engine(grid_of(inplace, abi.COMTOT_EXACT)) as e:
+        e.import_census(d6[:n], i5[:n], keys[:n])
+        check_stats(e, g1, 1)
+        check_comb(e, g, NG, pow2, salt, collect=True)
+        # roulette at one group: the floor at the lower quartile of ew removes some of the records below it
+        pre = e.census()
+        floor1 = np.full((NZ, NR, 1), np.quantile(pre[0][:, 4], 0.25))
+        r = e.census_roulette(g1, 1, floor1, salt)
+        keep, ew_r = PC.roulette_numpy(*pre, NZ, NR, g1, 1, floor1, salt)
+        assert (r["n_before"], r["n_after"]) == (n, int(keep.sum())) and 0 < n - r["n_after"] < n // 2
+        assert r["e_before"] == pytest.approx(pre[0][:, 4].sum(), rel=sum_tol(n), abs=0.0)
+        assert r["e_after"] == pytest.approx(ew_r[keep].sum(), rel=sum_tol(n), abs=0.0)
+        mid = e.census()                                                   # the survivors, in the order they took
+        o, om = np.argsort(pre[2]), np.argsort(mid[2])
+        np.testing.assert_array_equal(mid[2][om], pre[2][o][keep[o]])
+        np.testing.assert_array_equal(mid[0][om, 4].view(np.uint64), ew_r[o][keep[o]].view(np.uint64))
+        # split at 32 groups under ceilings 2^-40 of the pool's: nearly every record becomes 8
+        low = w * 2.0 ** -40
+        s = e.census_split(g, NG, low, MC, salt)
+        m, _, want = PC.split_numpy(*mid, NZ, NR, g, NG, low, MC, salt)
+        assert (s["n_before"], s["n_after"], s["n_split"]) == (len(mid[2]), len(want[2]), int((m > 1).sum()))
+        assert s["n_after"] > 5 * 1024 and e.census_count() == s["n_after"]
+        assert s["e_before"] == pytest.approx(mid[0][:, 4].sum(), rel=sum_tol(s["n_before"]), abs=0.0)
+        assert s["e_after"] == pytest.approx(want[0][:, 4].sum(), rel=sum_tol(s["n_before"]), abs=0.0)
+        same_census(e.census(), want)
+        check_stats(e, g, NG)
+        check_comb(e, g1, 1, np.full((NZ, NR, 1), 2.0 ** -10), salt, collect=False)
+
+
 # ------------------------------------------------- 10. unbiased in transport
 ENSEMBLE = 32
 ENSEMBLE_SEED = 4000
